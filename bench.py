@@ -2,6 +2,7 @@
 """Benchmark of the hot path: MH samples/sec of the HIP sampler (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--iters-per-step I] [--model 1|2] [--moments]
+                  [--dump-outputs DIR]
 
 A "step" is ONE pass of the sampler over the whole batch: every chain advanced by I Metropolis-Hastings iterations
 (thinned samples of all chains written to HBM).  The N=1 workload is the one BASELINE.json's metric is quoted on,
@@ -39,7 +40,7 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
-import pyhillfit_amd  # noqa: E402,F401  (sets the ROCm runtime defaults — hardware queues — before the first GPU call)
+import pyhillfit_amd  # noqa: E402,F401
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
 FP64_VALU_PEAK_TFLOPS = 78.6   # 256 CU x 64 fp64 FMA lanes x 2 x 2.4 GHz (vector, non-MFMA)
@@ -57,6 +58,8 @@ DEFAULT_ITERS = {"c2": 2000, "c3": 24000, "c4": 2000, "c5": 500, "s3": 4000, "s3
 OTHER_STEPS = {"c2": (250, 10), "c4": (12, 3), "c5": (12, 4), "c5_moments": (12, 4), "c3_model1": (3, 2), "s3": (6, 2), "s3h": (3, 1)}
 OTHER_SPECS = {"c2": ("c2", 2, False), "c4": ("c4", 2, False), "c5": ("c5", 2, False), "s3": ("s3", 2, False), "s3h": ("s3h", 2, False),          # name -> (workload, model, moments)
                "c5_moments": ("c5", 2, True), "c3_model1": ("c3", 1, False)}
+# --dump-outputs: 64 MB for all files together (c3's rows alone are 132 GB a step), headers included; seed of the sampled positions
+DUMP_BYTES, DUMP_HEADER_BYTES, DUMP_SEED = 64 * 10 ** 6, 256, 2025
 
 
 def profile_facts(workload, chains, iters, thinning):
@@ -155,7 +158,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="N = 1, c3: skip the short c2 / c4 / c5 regions after the headline")
     ap.add_argument("--single-region", action="store_true", help="N > 1: only the region --scaling names (no second region of the other kind)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the headline region, write what its last step computed on rank 0 "
+                    "(saved rows, their last row, per-chain acceptance) as DIR/<name>.npy, float64, 64 MB in all: arrays too large for "
+                    "their share as a fixed seeded sample")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def spawn_ranks(a):
@@ -247,6 +256,13 @@ class HierarchicalBatch(object):
         return [self.torch.empty((h.rows_between(0, I), h.Q, h.d + 1, h.C), dtype=self.torch.float64, device=self.dev)
                 for h in self.samplers]
 
+    def outputs(self):
+        """what a caller of the last step received, per launch group (self.samplers' order): the saved rows and the chains' acceptance"""
+        out = []
+        for j, (h, r) in enumerate(zip(self.samplers, self.rows)):
+            out += [("group%d_samples" % j, r), ("group%d_samples_last_row" % j, r[-1]), ("group%d_acceptance" % j, h.acceptance())]
+        return out
+
     def advance(self, I, out, join=True):
         # one HIP stream per Ne group: the small groups (Ne = 5, 6: tens of wavefronts) are latency-bound
         # and hide under the big Ne = 3 launch instead of queueing behind it.  join=False: the groups' streams are not joined
@@ -333,6 +349,10 @@ class SingleLevelBatch(object):
     def make_rows(self, I):
         s = self.s
         return self.torch.empty((s.rows_between(0, I), s.Q, s.d + 1, s.C), dtype=self.torch.float64, device=self.dev)
+
+    def outputs(self):
+        """what a caller of the last step received: the saved rows [R][Q][d+1][C] and the chains' acceptance [Q][C]"""
+        return [("samples", self.rows), ("samples_last_row", self.rows[-1]), ("acceptance", self.s.acceptance())]
 
     def advance(self, I, out, join=True):
         self.s.advance(I, out=out)
@@ -423,7 +443,7 @@ def timed_region(b, I, steps, warmup, ctx):
     Returns (seconds, kernel ms per step from HIP events on the launch stream(s), chains of all ranks)."""
     torch, dist, dev, world = ctx["torch"], ctx["dist"], ctx["dev"], ctx["world"]
     b.reserve((warmup + steps) * I)
-    rows = b.make_rows(I)
+    rows = b.rows = b.make_rows(I)                  # every step writes here: after the region it holds the last step's rows
     for _ in range(warmup):
         b.advance(I, out=rows)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
@@ -486,6 +506,26 @@ def rooflines(workload, b, I, thinning, kernel_ms):
     return roof, fp64
 
 
+def dump_outputs(arrays, directory):
+    """--dump-outputs: write (name, tensor) pairs as float64 DIR/<name>.npy, DUMP_BYTES in all.  The budget is shared out smallest
+    array first; an array larger than its share is written as a fixed sample of its flattened elements: one at a seeded random
+    position in each of `share / 8` equal parts of it.  Same arguments -> same positions, so two builds compare file by file."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    left, todo = DUMP_BYTES - DUMP_HEADER_BYTES * len(arrays), sorted(arrays, key=lambda nt: nt[1].numel())
+    for k, (name, t) in enumerate(todo):
+        share = left // (len(todo) - k)
+        flat = t.detach().to(torch.float64).reshape(-1)
+        n, m = flat.numel(), share // 8
+        if n > m:
+            edge = np.arange(m + 1, dtype=np.int64) * n // m
+            idx = np.random.default_rng(DUMP_SEED).integers(edge[:-1], edge[1:])
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a if n > m else a.reshape(tuple(t.shape)))
+        left -= a.nbytes
+
+
 def release(torch):
     gc.collect()
     torch.cuda.empty_cache()
@@ -533,7 +573,9 @@ def main():
     b = make_batch(a.workload, a.scaling, C, a, ctx)
     dt, kernel_ms, chains_total = timed_region(b, I, a.steps, a.warmup, ctx)
     # "gather samples/summaries" (RCCL, outside the timed region): per-problem mean acceptance of every rank to rank 0
-    acc = b.acceptance_summary().reshape(-1, 1)
+    acc = b.acceptance_summary().reshape(-1, 1)          # raises, as a caller's read would, if a queued launch drained
+    if a.dump_outputs and rank == 0:
+        dump_outputs(b.outputs(), a.dump_outputs)
     gathered = D.gather_rows(acc if backend == "nccl" or world == 1 else acc.cpu())
     out = None
     if rank == 0:

@@ -163,16 +163,19 @@ print("RCCL_WORLD1_OK")
 
 
 @pytest.mark.parametrize("workload", ["c3", "c4"])
-def test_bench_line_keeps_the_contract(workload):
+def test_bench_line_keeps_the_contract(workload, tmp_path):
     """`python bench.py` prints ONE JSON line with the keys the driver reads (metric, value, unit, n_gpus, steps, warmup, ms_per_step,
     higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus `roofline` and — at N = 1 — `cpu_baseline`; run small
-    (c3: the single-level queue path; c4: four kernels on four free-running streams) in a fresh process, as the driver does."""
+    (c3: the single-level queue path; c4: four kernels on four free-running streams) in a fresh process, as the driver does.
+    --dump-outputs writes the last step's rows (a sample of them), their last row and the acceptance per chain: float64, 64 MB in all."""
     import subprocess
     import sys
+    import bench
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
+    dump = str(tmp_path / "dump")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", workload,
-           "--chains", "128", "--iters-per-step", "400", "--no-cpu-baseline"]
+           "--chains", "128", "--iters-per-step", "400", "--no-cpu-baseline", "--dump-outputs", dump]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -190,6 +193,17 @@ def test_bench_line_keeps_the_contract(workload):
     chains = d["config"]["chains_per_gpu"]
     assert d["value"] == pytest.approx(chains * 400 * 2 / (d["ms_per_step"] * 2e-3), rel=1e-6)
     assert "other_workloads" not in d                       # only the default-size headline run carries the other configurations
+    files = sorted(os.listdir(dump))
+    groups = [""] if workload == "c3" else sorted({f.split("_")[0] + "_" for f in files})
+    assert files == sorted(g + n for g in groups for n in ("acceptance.npy", "samples.npy", "samples_last_row.npy"))
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in files) <= bench.DUMP_BYTES
+    chains = 0
+    for g in groups:
+        last, acc = np.load(os.path.join(dump, g + "samples_last_row.npy")), np.load(os.path.join(dump, g + "acceptance.npy"))
+        assert last.dtype == acc.dtype == np.float64 and last.ndim == 3 and acc.shape == (last.shape[0], 128) and last.shape[2] == 128
+        assert np.isfinite(last).all() and np.isfinite(np.load(os.path.join(dump, g + "samples.npy"))).all() and 0 < acc.mean() < 1
+        chains += acc.size
+    assert chains == d["config"]["chains_per_gpu"]
 
 
 def test_bench_default_line_carries_the_other_configurations():

@@ -459,3 +459,27 @@ def test_native_text_formatter_is_numpy_savetxt_byte_for_byte(tmp_path):
     assert open(str(tmp_path / "v.txt"), "rb").read() == want.getvalue()
     with pytest.raises(OSError):
         chainio.write_text(str(tmp_path / "no_such_dir" / "x.txt"), False, (), table[:2])
+
+
+def test_bench_dump_outputs_fits_its_budget_and_samples_fixed_positions(tmp_path):
+    """bench.py --dump-outputs: arrays within their share of the 64 MB are written whole, in their shape; a larger one as a sample at
+    seeded positions spread over all of it — the same positions in every run, so that two builds can be compared file by file"""
+    import torch
+    import bench
+    big = torch.arange(3 * 10 ** 7, dtype=torch.float64).reshape(10 ** 4, 3, 1000)      # 240 MB; every value is its own flat position
+    acc = torch.rand(7, 5, dtype=torch.float64)
+    arrays = [("samples", big), ("samples_last_row", big[-1]), ("acceptance", acc)]
+    for run in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / run))
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["acceptance.npy", "samples.npy", "samples_last_row.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / n)) for n in names) <= bench.DUMP_BYTES
+    for n in names:
+        x, y = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert x.dtype == np.float64 and np.array_equal(x, y), n
+    assert np.array_equal(np.load(str(tmp_path / "a" / "acceptance.npy")), acc.numpy())
+    assert np.array_equal(np.load(str(tmp_path / "a" / "samples_last_row.npy")), big[-1].numpy())
+    s = np.load(str(tmp_path / "a" / "samples.npy"))
+    assert s.ndim == 1 and s.nbytes > 0.9 * (bench.DUMP_BYTES - acc.numel() * 8 - 3000 * 8 - 3 * bench.DUMP_HEADER_BYTES)
+    assert np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < big.numel() and s[-1] > 0.99 * big.numel()   # distinct, in range, to the end
+    assert np.array_equal(s, big.reshape(-1)[torch.from_numpy(s.astype(np.int64))].numpy())
