@@ -362,6 +362,35 @@ int phf_predictive_accumulate(int num_problems, const double* rows, int64_t num_
                               int chains_used, int grid_points, const double* hill_x, const double* pic50_x, int chunk,
                               double* sums, double* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- convergence diagnostics: split-R-hat, multi-chain ESS, MCSE of the mean -------------------------------------------------
+ * The reference runs one chain per pair and computes none of these.  Per problem q and column j, over the post-burn-in rows
+ * x[m][n] of chains m = 0..C-1, n = 0..N-1: split-R-hat and multi-chain ESS as in the Stan reference manual (Gelman et al.,
+ * BDA3 11.4-11.5; Vehtari et al. 2021) WITHOUT rank normalisation.  Chain m gives half-chains 2m (rows 0..h-1) and 2m+1
+ * (rows N-h..N-1), h = floor(N/2) >= 4; the device accumulates, per half-chain, its mean and its autocovariance
+ * acov(k) = (1/h) sum_{n=0}^{h-1-k} (x_n - mean)(x_{n+k} - mean), k = 0..L, L = min(K, h-1), while the rows stream past
+ * (pyhillfit_amd/csrc/phf_diagnostics.hip); phf_diagnostics_reduce averages over the 2C half-chains and the host applies Geyer's
+ * initial positive / monotone sequence (pyhillfit_amd/diagnostics.py).  Deterministic: no atomics, and the result is bit-identical
+ * however the rows are cut into accumulate calls.
+ *   rows       device [num_rows][num_problems][row_stride_cols][num_chains] — the samplers' row buffer (single-level,
+ *              hierarchical and tempered alike) or a slice of it along the first axis; columns 0..num_columns-1 are diagnosed
+ *   first_row  index of rows[0] among the total_rows post-burn-in rows; calls must come in row order, each row exactly once
+ *   lags       the lag limit K (256 is the command lines' default)
+ *   workspace  device, at least phf_diagnostics_workspace_bytes(...) = num_problems * num_columns * num_chains * (4L + 6) doubles;
+ *              phf_diagnostics_init zeroes it (stream-ordered) before the first accumulate
+ *   out        device [num_problems][num_columns][L + 3]: mean over half-chains of acov(k) for k = 0..L, then the mean of the
+ *              half-chain means, then their variance with divisor 2C - 1 (= B/h); valid once all total_rows rows have arrived
+ * phf_diagnostics_workspace_bytes returns 0 for an invalid shape (phf_last_error() says why); phf_diagnostics_effective_lags
+ * returns L = min(K, floor(total_rows / 2) - 1) or a negative code. */
+size_t phf_diagnostics_workspace_bytes(int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags);
+int phf_diagnostics_effective_lags(int64_t total_rows, int lags);
+int phf_diagnostics_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags, double* workspace,
+                         size_t workspace_bytes, void* stream);
+int phf_diagnostics_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                               int num_columns, int64_t first_row, int64_t total_rows, int lags, double* workspace,
+                               size_t workspace_bytes, void* stream);
+int phf_diagnostics_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags, const double* workspace,
+                           size_t workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,13 +3,15 @@
     python -m pyhillfit_amd.PyHillFit --data-file ../data/crumb_data.csv -m 2 -a [--hierarchical]
            [-i 500000] [-t 5] [-b 4] [-c N] [-Ne 0] [--num-APs 500] [-bfo]
            [--num-chains 64 | 128 with --hierarchical] [--seed 25] [--device cuda:0] [--save-all-chains] [--segment 20000]
+           [--diagnostics [--diagnostic-lags 256]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
 kernels, `--num-chains` independent chains per pair.  What lands in the reference's chain file is chain 0 of the
 pair (burn-in removed exactly like PyHillFit.py:861-864); with --save-all-chains every chain is also written to
 `<chain file minus .txt>_all_chains.npy` ([rows][d+1][chains]); posterior moments of all chains, accumulated on the
-device, go to `<...>_summary.json`.  The CMA-ES start point is replaced by a deterministic least-squares fit
+device, go to `<...>_summary.json`; with --diagnostics, also split-R-hat / ESS / MCSE of every column over all chains
+(pyhillfit_amd/diagnostics.py), accumulated on the device segment by segment.  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -57,6 +59,9 @@ def build_parser():
     new.add_argument("--write-workers", type=int, default=None, help="processes formatting the chain text files (default: this rank's host cores - 1, at most 16; 0 = write in the main process)")
     new.add_argument("--save-all-chains", action='store_true', default=False, help="also write every chain to a .npy next to the chain file")
     new.add_argument("--segment", type=int, default=20000, help="MH iterations per kernel launch")
+    new.add_argument("--diagnostics", action='store_true', default=False, help="split-R-hat, multi-chain ESS and MCSE of every column over all chains, "
+                     "accumulated on the GPU while the rows stream past; written to the summary JSON as \"diagnostics\"")
+    new.add_argument("--diagnostic-lags", type=int, default=256, help="lag limit K of the autocorrelation sums of --diagnostics")
     new.add_argument("--fused-launch", choices=["auto", "on", "off"], default="auto",
                      help="--hierarchical: the launch groups the gfx950 code object has kernels for (Ne = 3; Ne = 4 with 4 + 4 + 4 + 1 / 2 / 3 points) through "
                           "ONE persistent grid per segment instead of a launch each (auto: when the run's chains give every SIMD a wavefront); same numbers")
@@ -135,6 +140,14 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             raise SystemExit("--save-all-chains needs {:.1f} GB of device memory for {} pairs x {} chains x {} saved rows, {:.1f} GB are free: "
                              "select fewer pairs (--drugs/--channels), fewer chains or a larger thinning".format(need / 1e9, Q, C, saved_iterations, free / 1e9))
     d = s.d
+    diag = None
+    if args.diagnostics:
+        from . import diagnostics as dg
+        diag_rows = saved_iterations - burn
+        dg.check_memory(dg.workspace_bytes(Q, d + 1, C, diag_rows, args.diagnostic_lags), device)
+        diag = dg.ChainDiagnostics(Q, C, d + 1, diag_rows, args.diagnostic_lags, device)
+        if burn == 0:
+            diag.accumulate(s.row0.unsqueeze(0).contiguous())
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
             chainio.host_buffer((saved_iterations, Q, d + 1, 1)))   # pinned: chain 0 leaves the GPU asynchronously
     kept[0] = s.row0 if keep_all else s.row0[:, :, :1].cpu()
@@ -147,6 +160,9 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         k = min(seg, total_iterations - done)
         nr = k // thinning
         rows = s.advance(k, out=buf[:nr])
+        first = max(0, burn - r)                                       # saved rows before `burn` are the burn-in
+        if diag is not None and first < nr:
+            diag.accumulate(rows[first:])
         # stream-ordered and asynchronous: the next segment is queued behind this copy while the host moves on (a blocking copy
         # here left the GPU idle for the gather + transfer + launch latency of every segment)
         kept[r:r + nr].copy_(rows if keep_all else rows[:, :, :, :1], non_blocking=True)
@@ -156,6 +172,7 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     mean, var, n_mom = s.posterior_moments()
     mean, var = mean.cpu().numpy(), var.cpu().numpy()
     acc = s.acceptance().cpu().numpy()
+    diag_res = diag.result() if diag is not None else None
     summaries = []
     for q, (d_clean, c_clean, chain_file) in enumerate(files):
         chain0 = kept[:, q, :, 0].cpu().numpy()
@@ -170,11 +187,15 @@ def run_single_level(pairs, args, device, rank=0, world=1):
                 "per_chain_mean_sd": mean[:, q].std(axis=1).tolist(), "acceptance": float(acc[q].mean()),
                 "start_point": np.asarray(theta0[q]).tolist(), "seed": args.seed,
                 "mh_samples_per_second": Q * C * total_iterations / elapsed}
+        if diag_res is not None:
+            summ["diagnostics"] = dg.json_record(diag_res, q, args.diagnostic_lags, saved_iterations - burn, C)
         with open(chain_file[:-4] + "_summary.json", "w") as f:
             json.dump(summ, f, indent=1)
         summaries.append(summ)
         print("\n\n{} + {} complete!\n\n".format(d_clean, c_clean))      # PyHillFit.py:970
     writers.close()
+    if diag_res is not None:
+        print(dg.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], diag_res["rhat"], diag_res["ess"]))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, Q * C, total_iterations, time.time() - start - elapsed))
     return summaries

@@ -8,7 +8,7 @@ t_i = (i/n)^c, n = 40, c = 3 (:151, doseresponse.py:27-28) through a process poo
 (times --num-chains chains, times all selected pairs) advance in one batch of HIP kernel launches; each rung's
 chain 0 is written, burn-in removed, headerless, to the reference's temperature_<t> chain file (:165-169), where
 python/compute_bayes_factors.py expects it.  Start point ones(d), identity covariance, mean reset at 1000*d
-(:63,80,114-115).  `--rungs N` changes n (BASELINE config 5 uses 32 rungs = --rungs 31).  `-nc N` — the reference's pool size —
+(:63,80,114-115).  `--diagnostics` adds split-R-hat / ESS / MCSE of every (pair, rung) over all its chains.  `--rungs N` changes n (BASELINE config 5 uses 32 rungs = --rungs 31).  `-nc N` — the reference's pool size —
 starts min(N, visible GPUs) ranks, one per GPU, which share the (pair, rung) units; or launch under torchrun."""
 import argparse
 import json
@@ -50,6 +50,9 @@ def build_parser():
     new.add_argument("--write-workers", type=int, default=None, help="processes formatting the chain text files (default: host cores - 1, at most 16; 0 = main process)")
     new.add_argument("--segment", type=int, default=20000)
     new.add_argument("--output-root", type=str, default="output")
+    new.add_argument("--diagnostics", action='store_true', default=False, help="split-R-hat, multi-chain ESS and MCSE of every column of every rung over "
+                     "all chains, accumulated on the GPU; written to thermodynamic_integration.json (one object per rung) and the rung records")
+    new.add_argument("--diagnostic-lags", type=int, default=256, help="lag limit K of the autocorrelation sums of --diagnostics")
     return parser
 
 
@@ -99,6 +102,19 @@ def assemble_thermodynamic_integration(unit_rows, pairs, temperatures, model, ru
     return rungs, tis
 
 
+def attach_diagnostics(rungs, tis, unit_rows, width, cols, R, chains, total_rows, lags):
+    """the gathered per-unit diagnostics (columns width.. of unit_rows: rhat, ess, mcse, lag_limit_reached per column) onto the
+    per-rung records and, one object per rung in temperature order, onto each pair's thermodynamic-integration record"""
+    from . import diagnostics as dg
+    unit_rows = unit_rows[np.lexsort((unit_rows[:, 1], unit_rows[:, 0]))]
+    v = unit_rows[:, width:].reshape(len(unit_rows), 4, cols)
+    res = {"rhat": v[:, 0], "ess": v[:, 1], "mcse_mean": v[:, 2], "lag_limit_reached": v[:, 3] != 0}
+    for u, rec in enumerate(rungs):
+        rec["diagnostics"] = dg.json_record(res, u, lags, total_rows, chains, columns=dr.file_labels + ["log-target"])
+    for ip, ti in enumerate(tis):
+        ti["diagnostics"] = [rungs[ip * R + ir]["diagnostics"] for ir in range(R)]
+
+
 def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     """pairs: [(drug, channel)] of the WHOLE run; one problem per (pair, rung), this rank's share of them sampled here.
     Every rank writes the chain files of its own units; rank 0 gathers the per-unit expectations, writes one
@@ -122,6 +138,9 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     num_saved = total_iterations // thinning + 1                                                    # :70
     burn = num_saved // args.burn_in_fraction                                                       # :71
     unit_rows = np.zeros((len(mine), 4 + d + 1 + 1))
+    width = unit_rows.shape[1]
+    if args.diagnostics:          # per unit and column: rhat, ess, mcse, lag_limit_reached; they ride on the one gather of unit rows
+        unit_rows = np.concatenate([unit_rows, np.zeros((len(mine), 4 * (d + 1)))], axis=1)
     mcmc_time = 0.0
     if len(mine):
         packed = dr.PackedPoints([(loaded[ip][2], loaded[ip][3]) for ip in my_pairs])
@@ -141,12 +160,22 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
         writers = chainio.WriterPool(args.write_workers if args.write_workers is not None else chainio.default_write_workers(world))
         seg = max(thinning, args.segment - args.segment % thinning)
         buf = torch.empty((seg // thinning, Q, d + 1, C), dtype=torch.float64, device=device)
+        diag = None
+        if args.diagnostics:
+            from . import diagnostics as dg
+            dg.check_memory(dg.workspace_bytes(Q, d + 1, C, num_saved - burn, args.diagnostic_lags), device)
+            diag = dg.ChainDiagnostics(Q, C, d + 1, num_saved - burn, args.diagnostic_lags, device)
+            if burn == 0:
+                diag.accumulate(s.row0.unsqueeze(0).contiguous())
         done, r = 0, 1
         start = time.time()
         while done < total_iterations:
             k = min(seg, total_iterations - done)
             nr = k // thinning
             rows = s.advance(k, out=buf[:nr])
+            first = max(0, burn - r)                                    # saved rows before `burn` are the burn-in
+            if diag is not None and first < nr:
+                diag.accumulate(rows[first:])
             kept[r:r + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # stream-ordered; the next segment is queued behind it at once
             done += k; r += nr
         torch.cuda.synchronize(device)
@@ -155,6 +184,11 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
         mean, var, _ = s.posterior_moments()
         mean = mean.cpu().numpy()
         ll1 = s.mean_log_likelihood_t1().cpu().numpy()            # [Q][C]  E_rung[log L(theta; t=1)], fused into the sampler
+        if diag is not None:
+            res = diag.result()
+            unit_rows[:, width:] = np.concatenate([res["rhat"], res["ess"], res["mcse_mean"], res["lag_limit_reached"].astype(np.float64)], axis=1)
+            print(dg.report_line(rank, ["{} + {} at t = {:g}".format(loaded[int(u) // R][0], loaded[int(u) // R][1], temperatures[int(u) % R])
+                                        for u in mine], res["rhat"], res["ess"]))
         for q, u in enumerate(mine):
             ip, ir = int(u) // R, int(u) % R
             drug, channel = loaded[ip][0], loaded[ip][1]
@@ -170,7 +204,10 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     if rank != 0:
         return []
     facts = {"chains": C, "iterations": total_iterations, "thinning": thinning, "burn_in_fraction": args.burn_in_fraction, "ranks": world}
-    out, tis = assemble_thermodynamic_integration(np.concatenate(gathered), [(l[0], l[1]) for l in loaded], temperatures, model, facts)
+    gathered = np.concatenate(gathered)
+    out, tis = assemble_thermodynamic_integration(gathered[:, :width], [(l[0], l[1]) for l in loaded], temperatures, model, facts)
+    if args.diagnostics:
+        attach_diagnostics(out, tis, gathered, width, d + 1, R, C, num_saved - burn, args.diagnostic_lags)
     for (drug, channel, _, _), ti in zip(loaded, tis):
         with open(thermodynamic_integration_file(model, drug, channel), "w") as f:
             json.dump(ti, f, indent=1)

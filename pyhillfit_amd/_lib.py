@@ -12,7 +12,9 @@ ABI_VERSION = 7
 EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_state_size", "phf_single_level_init",
            "phf_single_level_advance", "phf_single_level_advance_queued", "phf_single_level_queue_status", "phf_single_level_last_kernel", "phf_single_level_log_target",
            "phf_debug_math", "phf_debug_isa", "phf_philox_rounds", "phf_debug_philox", "phf_debug_philox_rounds", "phf_hierarchical_state_size", "phf_hierarchical_init", "phf_hierarchical_advance", "phf_hierarchical_advance_queued", "phf_hierarchical_queue_words", "phf_hierarchical_advance_fused", "phf_hierarchical_fused_queue_words",
-           "phf_hierarchical_set_kernel_policy", "phf_hierarchical_last_kernel", "phf_hierarchical_log_target", "phf_predictive_scratch_bytes", "phf_predictive_accumulate"]
+           "phf_hierarchical_set_kernel_policy", "phf_hierarchical_last_kernel", "phf_hierarchical_log_target", "phf_predictive_scratch_bytes", "phf_predictive_accumulate",
+           "phf_diagnostics_workspace_bytes", "phf_diagnostics_effective_lags", "phf_diagnostics_init", "phf_diagnostics_accumulate",
+           "phf_diagnostics_reduce"]
 
 
 class PhfError(RuntimeError):
@@ -77,6 +79,12 @@ def load():
     lib.phf_predictive_scratch_bytes.argtypes = [i32, i64, i32, i32]
     lib.phf_predictive_scratch_bytes.restype = C.c_size_t
     lib.phf_predictive_accumulate.argtypes = [i32, vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, C.c_size_t, vp]
+    lib.phf_diagnostics_workspace_bytes.argtypes = [i32, i32, i32, i64, i32]
+    lib.phf_diagnostics_workspace_bytes.restype = C.c_size_t
+    lib.phf_diagnostics_effective_lags.argtypes = [i64, i32]
+    lib.phf_diagnostics_init.argtypes = [i32, i32, i32, i64, i32, vp, C.c_size_t, vp]
+    lib.phf_diagnostics_accumulate.argtypes = [vp, i64, i32, i32, i32, i32, i64, i64, i32, vp, C.c_size_t, vp]
+    lib.phf_diagnostics_reduce.argtypes = [i32, i32, i32, i64, i32, vp, C.c_size_t, vp, vp]
     _lib = lib
     return lib
 

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, bestfit, chainio
+from . import diagnostics as dg
 from . import doseresponse as dr
 from .sampler import _ptr, _stream_ptr, gamma_table, raise_if_drained
 
@@ -432,6 +433,11 @@ def cdf_chains(args, num_chains):
 
 
 # ---- driver ------------------------------------------------------------------------------------------------------------
+def hierarchical_columns(ne):
+    """the columns of a hierarchical row (chainio.HIERARCHICAL_HEADER)"""
+    return ["alpha", "beta", "mu", "s"] + [n for e in range(1, ne + 1) for n in ("pic50_%d" % e, "hill_%d" % e)] + ["sigma", "log-target"]
+
+
 def run_hierarchical(pairs, args, device, rank=0, world=1):
     """All pairs of this rank — replaces python/PyHillFit.py:213-642 run per pair."""
     t_begin = time.time()
@@ -500,8 +506,14 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             curves = PredictiveCurves(Q, device)
             if burn == 0:
                 curves.accumulate(s.row0.unsqueeze(0).contiguous(), cdf_chains(args, C))
+        diag = None
+        if getattr(args, "diagnostics", False):                        # split-R-hat / ESS / MCSE over all chains, accumulated like the curves
+            dg.check_memory(dg.workspace_bytes(Q, d + 1, C, saved_iterations - burn, args.diagnostic_lags), device)
+            diag = dg.ChainDiagnostics(Q, C, d + 1, saved_iterations - burn, args.diagnostic_lags, device)
+            if burn == 0:
+                diag.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         stream=torch.cuda.Stream(device=device)))
+                         diag=diag, stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
     fused = None
@@ -550,6 +562,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                 first = max(0, burn - run["r"])                        # saved rows before `burn` are the burn-in (:84-86 of the CDF script)
                 if run["curves"] is not None and first < nr:
                     run["curves"].accumulate(rows[first:], cdf_chains(args, args.num_chains))
+                if run["diag"] is not None and first < nr:
+                    run["diag"].accumulate(rows[first:])
                 run["kept"][run["r"]:run["r"] + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # chain 0 of each pair
                 ev = torch.cuda.Event()
                 ev.record(run["stream"])
@@ -566,12 +580,16 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         fused.check_queue()
     elapsed = time.time() - start
     total_chains = sum(len(r_["members"]) for r_ in runs) * args.num_chains
+    diag_names, diag_parts = [], []
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
         Q, C = len(members), args.num_chains
         mean, var, _ = s.posterior_moments()
         mean, var = mean.cpu().numpy(), var.cpu().numpy()
         acc = s.acceptance().cpu().numpy()
+        diag_res = run["diag"].result() if run["diag"] is not None else None
+        if diag_res is not None:
+            run["diag"].free()
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
@@ -585,11 +603,18 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     "pooled_sd": np.sqrt(var[:, q].mean(axis=1) + mean[:, q].var(axis=1)).tolist(),
                     "acceptance": float(acc[q].mean()), "first_iteration": theta0[q].tolist(),
                     "mh_samples_per_second": total_chains * total_iterations / elapsed}
+            if diag_res is not None:
+                summ["diagnostics"] = dg.json_record(diag_res, q, args.diagnostic_lags, saved_iterations - burn, C,
+                                                     columns=hierarchical_columns(ne))
+                diag_names.append("{} + {}".format(d_clean, c_clean))
+                diag_parts.append((diag_res["rhat"][q], diag_res["ess"][q]))
             with open(chain_file[:-4] + "_summary.json", "w") as f:
                 json.dump(summ, f, indent=1)
             summaries.append(summ)
     writers.close()
     chain_streams.close()
+    if getattr(args, "diagnostics", False):
+        print(dg.report_line(rank, diag_names, [p_[0] for p_ in diag_parts], [p_[1] for p_ in diag_parts]))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, total_chains, total_iterations, time.time() - start - elapsed))
     return summaries
