@@ -391,6 +391,58 @@ int phf_diagnostics_accumulate(const double* rows, int64_t num_rows, int num_pro
 int phf_diagnostics_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags, const double* workspace,
                            size_t workspace_bytes, double* out, void* stream);
 
+/* ---- pointwise log-likelihood and WAIC -------------------------------------------------------------------------------------
+ * The terms are per DATA POINT (not per merged entry).  Points of problem q are row q of the arrays, in any order the caller keeps
+ * (pyhillfit_amd/waic.py: data-file order); point p < count[q] of problem q has log-likelihood, for one parameter vector:
+ *   single-level (model 1: theta = (pIC50, sigma), Hill = 1; model 2: theta = (pIC50, Hill, sigma)), pred = the Hill curve in percent,
+ *     tag 0 (0 < y < 100):  -ln(2 pi)/2 - ln sigma - (y - pred)^2 / (2 sigma^2)
+ *     tag 1 (y == 0):       ln Phi((0 - pred)/sigma)          tag 2 (y == 100): ln Phi((pred - 100)/sigma)
+ *     (points outside [0, 100] are the caller's to drop, as the sampler drops them; sigma <= 1e-3 gives -inf).  Their sum over a
+ *     pair's points is the sampler's t = 1 log-likelihood + (n_total - n_uncensored) ln(2 pi)/2: the reference's pi_bit charges
+ *     ln(2 pi)/2 to censored and dropped points too.
+ *   hierarchical (theta = [alpha, beta, mu, s, pIC50_1, Hill_1, ..., pIC50_Ne, Hill_Ne, sigma]), tag = the point's experiment i:
+ *     -ln(2 pi)/2 - ln sigma - (y - pred_i)^2 / (2 sigma^2) - ln(Phi((100 - pred_i)/sigma) - Phi((0 - pred_i)/sigma)),
+ *     the truncated-normal density of the hierarchical likelihood (sigma <= 1e-3 gives -inf).
+ * Device arrays; count[q] is clamped to [0, stride] and a tag outside its range to the nearest valid one (no access out of bounds). */
+typedef struct phf_pointwise_points {
+  int32_t num_problems;
+  int32_t stride;              /* points per problem row (>= every count) */
+  const double* ln_conc;       /* [num_problems][stride] natural log of the concentration */
+  const double* response;      /* [num_problems][stride] */
+  const int32_t* tag;          /* [num_problems][stride] single-level: 0 | 1 | 2 as above; hierarchical: experiment index 0..Ne-1 */
+  const int32_t* count;        /* [num_problems] points of each problem */
+} phf_pointwise_points;
+
+/* Batch evaluators: out[i][p] = log-likelihood of point p of problem problem_index[i] at theta[.][i] ([d][m], column i = vector i;
+ * d = model + 1, or 5 + 2 num_expts); out is [m][stride], NaN for p >= count.  Serve the tests and the chain-file tool. */
+int phf_pointwise_loglik_single_level(const phf_pointwise_points* pts, int model, int64_t m, const int32_t* problem_index,
+                                      const double* theta, double* out, void* stream);
+int phf_pointwise_loglik_hierarchical(const phf_pointwise_points* pts, int num_expts, int64_t m, const int32_t* problem_index,
+                                      const double* theta, double* out, void* stream);
+
+/* Streaming WAIC accumulator (pyhillfit_amd/csrc/phf_pointwise.hip).  Over the S = total_rows x num_chains draws of problem q,
+ * per point p: LSE_p = ln sum_draws exp(l_p) and var_p = the variance of l_p over the draws (divisor S - 1).
+ *   likelihood  1 | 2: single-level model 1 | 2, theta = columns 0..model of a row;
+ *               3: hierarchical with num_expts = Ne experiments, pIC50_i = column 4 + 2i, Hill_i = 5 + 2i, sigma = 4 + 2 Ne
+ *   rows        device [num_rows][num_problems][row_stride_cols][num_chains] — the samplers' row buffer or a slice of it along the
+ *               first axis (the layout phf_diagnostics_accumulate reads), problem q <-> row q of pts
+ *   first_row   index of rows[0] among the total_rows rows; calls come in row order, each row exactly once
+ *   workspace   device, phf_waic_workspace_bytes(...) = num_problems * stride * 5 * num_chains doubles: per (problem, point, chain) a
+ *               running max and the sum of exp(l - max) (online log-sum-exp), the first l and the sums of (l - first) and its square;
+ *               phf_waic_init zeroes it (stream-ordered) before the first accumulate
+ *   out         device [2][num_problems][stride]: LSE_p, then var_p; valid once all total_rows rows have arrived (meaningless for p >= count)
+ * Deterministic: no atomics, every accumulator is produced by one lane in row order and round-trips through HBM exactly; the chains
+ * are merged in a fixed order.  Bit-identical however the rows are cut into calls.  An invalid shape gives 0 bytes /
+ * PHF_ERR_INVALID_ARGUMENT without touching a GPU (phf_last_error() says why). */
+size_t phf_waic_workspace_bytes(int num_problems, int stride, int num_chains, int64_t total_rows);
+int phf_waic_init(int num_problems, int stride, int num_chains, int64_t total_rows, double* workspace, size_t workspace_bytes,
+                  void* stream);
+int phf_waic_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
+                        int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, double* workspace,
+                        size_t workspace_bytes, void* stream);
+int phf_waic_reduce(int num_problems, int stride, int num_chains, int64_t total_rows, const double* workspace, size_t workspace_bytes,
+                    double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
     python -m pyhillfit_amd.PyHillFit --data-file ../data/crumb_data.csv -m 2 -a [--hierarchical]
            [-i 500000] [-t 5] [-b 4] [-c N] [-Ne 0] [--num-APs 500] [-bfo]
            [--num-chains 64 | 128 with --hierarchical] [--seed 25] [--device cuda:0] [--save-all-chains] [--segment 20000]
-           [--diagnostics [--diagnostic-lags 256]]
+           [--diagnostics [--diagnostic-lags 256]] [--waic]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -11,7 +11,8 @@ kernels, `--num-chains` independent chains per pair.  What lands in the referenc
 pair (burn-in removed exactly like PyHillFit.py:861-864); with --save-all-chains every chain is also written to
 `<chain file minus .txt>_all_chains.npy` ([rows][d+1][chains]); posterior moments of all chains, accumulated on the
 device, go to `<...>_summary.json`; with --diagnostics, also split-R-hat / ESS / MCSE of every column over all chains
-(pyhillfit_amd/diagnostics.py), accumulated on the device segment by segment.  The CMA-ES start point is replaced by a deterministic least-squares fit
+(pyhillfit_amd/diagnostics.py), accumulated on the device segment by segment; with --waic, WAIC and the pointwise predictive
+accuracy of every data point over all chains (pyhillfit_amd/waic.py), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -62,6 +63,8 @@ def build_parser():
     new.add_argument("--diagnostics", action='store_true', default=False, help="split-R-hat, multi-chain ESS and MCSE of every column over all chains, "
                      "accumulated on the GPU while the rows stream past; written to the summary JSON as \"diagnostics\"")
     new.add_argument("--diagnostic-lags", type=int, default=256, help="lag limit K of the autocorrelation sums of --diagnostics")
+    new.add_argument("--waic", action='store_true', default=False, help="WAIC, p_waic and the pointwise elpd of every data point over all "
+                     "chains' post-burn-in draws, accumulated on the GPU while the rows stream past; written to the summary JSON as \"waic\"")
     new.add_argument("--fused-launch", choices=["auto", "on", "off"], default="auto",
                      help="--hierarchical: the launch groups the gfx950 code object has kernels for (Ne = 3; Ne = 4 with 4 + 4 + 4 + 1 / 2 / 3 points) through "
                           "ONE persistent grid per segment instead of a launch each (auto: when the run's chains give every SIMD a wavefront); same numbers")
@@ -148,6 +151,14 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         diag = dg.ChainDiagnostics(Q, C, d + 1, diag_rows, args.diagnostic_lags, device)
         if burn == 0:
             diag.accumulate(s.row0.unsqueeze(0).contiguous())
+    waic = None
+    if getattr(args, "waic", False):
+        from . import waic as wc
+        wpts = wc.Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))
+        wc.check_memory(wc.workspace_bytes(Q, wpts.stride, C, saved_iterations - burn), device)
+        waic = wc.PointwiseWAIC(wpts, model, Q, C, saved_iterations - burn, device)
+        if burn == 0:
+            waic.accumulate(s.row0.unsqueeze(0).contiguous())
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
             chainio.host_buffer((saved_iterations, Q, d + 1, 1)))   # pinned: chain 0 leaves the GPU asynchronously
     kept[0] = s.row0 if keep_all else s.row0[:, :, :1].cpu()
@@ -163,6 +174,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         first = max(0, burn - r)                                       # saved rows before `burn` are the burn-in
         if diag is not None and first < nr:
             diag.accumulate(rows[first:])
+        if waic is not None and first < nr:
+            waic.accumulate(rows[first:])
         # stream-ordered and asynchronous: the next segment is queued behind this copy while the host moves on (a blocking copy
         # here left the GPU idle for the gather + transfer + launch latency of every segment)
         kept[r:r + nr].copy_(rows if keep_all else rows[:, :, :, :1], non_blocking=True)
@@ -173,6 +186,7 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     mean, var = mean.cpu().numpy(), var.cpu().numpy()
     acc = s.acceptance().cpu().numpy()
     diag_res = diag.result() if diag is not None else None
+    waic_res = waic.result() if waic is not None else None
     summaries = []
     for q, (d_clean, c_clean, chain_file) in enumerate(files):
         chain0 = kept[:, q, :, 0].cpu().numpy()
@@ -189,6 +203,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
                 "mh_samples_per_second": Q * C * total_iterations / elapsed}
         if diag_res is not None:
             summ["diagnostics"] = dg.json_record(diag_res, q, args.diagnostic_lags, saved_iterations - burn, C)
+        if waic_res is not None:
+            summ["waic"] = wc.json_record(waic_res[q], wpts, q)
         with open(chain_file[:-4] + "_summary.json", "w") as f:
             json.dump(summ, f, indent=1)
         summaries.append(summ)
@@ -196,9 +212,19 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     writers.close()
     if diag_res is not None:
         print(dg.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], diag_res["rhat"], diag_res["ess"]))
+    if waic_res is not None:
+        print(wc.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], waic_res))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, Q * C, total_iterations, time.time() - start - elapsed))
     return summaries
+
+
+def experiments_and_labels(drug, channel, num_expts=None):
+    """the experiments the sampler concatenates for a pair (PyHillFit.py:661-665; the first num_expts of them if given) and their
+    labels in the data file"""
+    n, numbers, experiments = dr.load_crumb_data(drug, channel)
+    n = n if num_expts is None else num_expts
+    return list(experiments[:n]), [int(e) + 1 for e in numbers[:n]]
 
 
 def pairs_with_ids(all_pairs, loaded):

@@ -14,7 +14,8 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_debug_math", "phf_debug_isa", "phf_philox_rounds", "phf_debug_philox", "phf_debug_philox_rounds", "phf_hierarchical_state_size", "phf_hierarchical_init", "phf_hierarchical_advance", "phf_hierarchical_advance_queued", "phf_hierarchical_queue_words", "phf_hierarchical_advance_fused", "phf_hierarchical_fused_queue_words",
            "phf_hierarchical_set_kernel_policy", "phf_hierarchical_last_kernel", "phf_hierarchical_log_target", "phf_predictive_scratch_bytes", "phf_predictive_accumulate",
            "phf_diagnostics_workspace_bytes", "phf_diagnostics_effective_lags", "phf_diagnostics_init", "phf_diagnostics_accumulate",
-           "phf_diagnostics_reduce"]
+           "phf_diagnostics_reduce", "phf_pointwise_loglik_single_level", "phf_pointwise_loglik_hierarchical", "phf_waic_workspace_bytes",
+           "phf_waic_init", "phf_waic_accumulate", "phf_waic_reduce"]
 
 
 class PhfError(RuntimeError):
@@ -24,6 +25,11 @@ class PhfError(RuntimeError):
 class Points(C.Structure):
     _fields_ = [("num_pairs", C.c_int32), ("stride", C.c_int32), ("ln_conc", C.c_void_p), ("response", C.c_void_p),
                 ("weight", C.c_void_p), ("counts", C.c_void_p), ("pi_bit", C.c_void_p), ("extra", C.c_void_p)]
+
+
+class PointwisePoints(C.Structure):
+    _fields_ = [("num_problems", C.c_int32), ("stride", C.c_int32), ("ln_conc", C.c_void_p), ("response", C.c_void_p),
+                ("tag", C.c_void_p), ("count", C.c_void_p)]
 
 
 class Problems(C.Structure):
@@ -85,6 +91,14 @@ def load():
     lib.phf_diagnostics_init.argtypes = [i32, i32, i32, i64, i32, vp, C.c_size_t, vp]
     lib.phf_diagnostics_accumulate.argtypes = [vp, i64, i32, i32, i32, i32, i64, i64, i32, vp, C.c_size_t, vp]
     lib.phf_diagnostics_reduce.argtypes = [i32, i32, i32, i64, i32, vp, C.c_size_t, vp, vp]
+    pwp = C.POINTER(PointwisePoints)
+    lib.phf_pointwise_loglik_single_level.argtypes = [pwp, i32, i64, vp, vp, vp, vp]
+    lib.phf_pointwise_loglik_hierarchical.argtypes = [pwp, i32, i64, vp, vp, vp, vp]
+    lib.phf_waic_workspace_bytes.argtypes = [i32, i32, i32, i64]
+    lib.phf_waic_workspace_bytes.restype = C.c_size_t
+    lib.phf_waic_init.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp]
+    lib.phf_waic_accumulate.argtypes = [pwp, i32, i32, vp, i64, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
+    lib.phf_waic_reduce.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
     _lib = lib
     return lib
 

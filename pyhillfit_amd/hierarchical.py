@@ -512,8 +512,17 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             diag = dg.ChainDiagnostics(Q, C, d + 1, saved_iterations - burn, args.diagnostic_lags, device)
             if burn == 0:
                 diag.accumulate(s.row0.unsqueeze(0).contiguous())
+        waic = None
+        if getattr(args, "waic", False):                               # WAIC over all chains, accumulated like the diagnostics
+            from . import waic as wc
+            from .PyHillFit import experiments_and_labels
+            wpts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
+            wc.check_memory(wc.workspace_bytes(Q, wpts.stride, C, saved_iterations - burn), device)
+            waic = wc.PointwiseWAIC(wpts, "hierarchical", Q, C, saved_iterations - burn, device)
+            if burn == 0:
+                waic.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, stream=torch.cuda.Stream(device=device)))
+                         diag=diag, waic=waic, stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
     fused = None
@@ -564,6 +573,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     run["curves"].accumulate(rows[first:], cdf_chains(args, args.num_chains))
                 if run["diag"] is not None and first < nr:
                     run["diag"].accumulate(rows[first:])
+                if run["waic"] is not None and first < nr:
+                    run["waic"].accumulate(rows[first:])
                 run["kept"][run["r"]:run["r"] + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # chain 0 of each pair
                 ev = torch.cuda.Event()
                 ev.record(run["stream"])
@@ -581,6 +592,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     elapsed = time.time() - start
     total_chains = sum(len(r_["members"]) for r_ in runs) * args.num_chains
     diag_names, diag_parts = [], []
+    waic_names, waic_parts = [], []
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
         Q, C = len(members), args.num_chains
@@ -590,6 +602,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         diag_res = run["diag"].result() if run["diag"] is not None else None
         if diag_res is not None:
             run["diag"].free()
+        waic_res = run["waic"].result() if run["waic"] is not None else None
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
@@ -608,6 +621,11 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                                                      columns=hierarchical_columns(ne))
                 diag_names.append("{} + {}".format(d_clean, c_clean))
                 diag_parts.append((diag_res["rhat"][q], diag_res["ess"][q]))
+            if waic_res is not None:
+                from . import waic as wc
+                summ["waic"] = wc.json_record(waic_res[q], run["waic"].points, q)
+                waic_names.append("{} + {}".format(d_clean, c_clean))
+                waic_parts.append(waic_res[q])
             with open(chain_file[:-4] + "_summary.json", "w") as f:
                 json.dump(summ, f, indent=1)
             summaries.append(summ)
@@ -615,6 +633,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     chain_streams.close()
     if getattr(args, "diagnostics", False):
         print(dg.report_line(rank, diag_names, [p_[0] for p_ in diag_parts], [p_[1] for p_ in diag_parts]))
+    if getattr(args, "waic", False):
+        from . import waic as wc
+        print(wc.report_line(rank, waic_names, waic_parts))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, total_chains, total_iterations, time.time() - start - elapsed))
     return summaries
