@@ -140,6 +140,103 @@ PHF_HD void phf_sl_log_target(int model, const double* lc, const double* y, cons
   *out_prior = outside ? -PHF_INF : lp;
 }
 
+/* phf_sl_log_target with the censored entries' Hill denominators shared: the same arguments, results and fp64 operations, except
+ * that a censored entry whose bit m (m = its index among the censored entries) is set in share_mask does not evaluate phf_hill_den
+ * but takes den_slot[den_off[m]], the denominator an uncensored entry at the same ln_conc BITS left there in this call
+ * (phf_hill_den is a pure function of (ln_conc, theta): it is the same double).  When share_mask != 0 every uncensored entry j stores
+ * its denominator at den_slot[j * slot_stride]; den_slot must hold n_other such slots.  Entries keep their order, and so do both sums.
+ * The samplers pass a compile-time share_mask (the mask folds away) and per-wavefront LDS slots (slot_stride = lanes of the block). */
+#define PHF_SHARE_PUT_(jj, d_) do { if (share_mask) den_slot[(jj) * slot_stride] = (d_); } while (0)
+#define PHF_CDEN_(jj) ((((share_mask) >> ((jj) - n_other)) & 1u) ? den_slot[den_off[(jj) - n_other]] \
+                                                                 : phf_hill_den(model, lc[jj], hill, ln_ic50, k_exp))
+PHF_HD void phf_sl_log_target_shared(int model, const double* lc, const double* y, const double* w, int n_other, int n_cens,
+                                     double n_other_points, double ss_within, double pi_bit, double temperature,
+                                     const double* th, phf_ktab k_exp, phf_ktab k_log,
+                                     unsigned share_mask, const int* den_off, double* den_slot, int slot_stride,
+                                     double* out_lik, double* out_prior, double* out_ll1) {
+  const double pic50 = th[0];
+  const double hill = (model == 1) ? 1.0 : th[1];
+  const double sigma = (model == 1) ? th[1] : th[2];
+  const double ln_ic50 = PHF_LN10 * (6.0 - pic50);
+  const double sl = sigma - PHF_SIGMA_LOC;
+  const double inv_s = phf_rcp(sigma);
+  const double log_sigma = phf_log_pos_k(sigma, k_log);
+  const double log_sl = phf_log_pos_k(sl, k_log);
+
+  double sse = ss_within, cens = 0.0;
+  int j = 0;
+  for (; j + 4 <= n_other; j += 4) {
+    const phf_ktab ke = k_exp;
+    const double d0 = phf_hill_den(model, lc[j], hill, ln_ic50, ke), d1 = phf_hill_den(model, lc[j + 1], hill, ln_ic50, ke);
+    const double d2 = phf_hill_den(model, lc[j + 2], hill, ln_ic50, ke), d3 = phf_hill_den(model, lc[j + 3], hill, ln_ic50, ke);
+    PHF_SHARE_PUT_(j, d0); PHF_SHARE_PUT_(j + 1, d1); PHF_SHARE_PUT_(j + 2, d2); PHF_SHARE_PUT_(j + 3, d3);
+    const double p01 = d0 * d1, p23 = d2 * d3;
+    const double inv = phf_rcp(p01 * p23);
+    const double i01 = inv * p23, i23 = inv * p01;
+    const double r0 = y[j] - PHF_PCT_(i01 * d1), r1 = y[j + 1] - PHF_PCT_(i01 * d0);
+    const double r2 = y[j + 2] - PHF_PCT_(i23 * d3), r3 = y[j + 3] - PHF_PCT_(i23 * d2);
+    sse = phf_fma(w[j] * r0, r0, sse); sse = phf_fma(w[j + 1] * r1, r1, sse);
+    sse = phf_fma(w[j + 2] * r2, r2, sse); sse = phf_fma(w[j + 3] * r3, r3, sse);
+  }
+  const int rem = n_other - j;
+  if (rem == 3) {
+    const phf_ktab ke = k_exp;
+    const double d0 = phf_hill_den(model, lc[j], hill, ln_ic50, ke), d1 = phf_hill_den(model, lc[j + 1], hill, ln_ic50, ke);
+    const double d2 = phf_hill_den(model, lc[j + 2], hill, ln_ic50, ke);
+    PHF_SHARE_PUT_(j, d0); PHF_SHARE_PUT_(j + 1, d1); PHF_SHARE_PUT_(j + 2, d2);
+    const double p01 = d0 * d1;
+    const double inv = phf_rcp(p01 * d2);
+    const double i01 = inv * d2;
+    const double r0 = y[j] - PHF_PCT_(i01 * d1), r1 = y[j + 1] - PHF_PCT_(i01 * d0);
+    const double r2 = y[j + 2] - PHF_PCT_(inv * p01);
+    sse = phf_fma(w[j] * r0, r0, sse); sse = phf_fma(w[j + 1] * r1, r1, sse); sse = phf_fma(w[j + 2] * r2, r2, sse);
+  } else if (rem == 2) {
+    const phf_ktab ke = k_exp;
+    const double d0 = phf_hill_den(model, lc[j], hill, ln_ic50, ke), d1 = phf_hill_den(model, lc[j + 1], hill, ln_ic50, ke);
+    PHF_SHARE_PUT_(j, d0); PHF_SHARE_PUT_(j + 1, d1);
+    const double inv = phf_rcp(d0 * d1);
+    const double r0 = y[j] - PHF_PCT_(inv * d1), r1 = y[j + 1] - PHF_PCT_(inv * d0);
+    sse = phf_fma(w[j] * r0, r0, sse); sse = phf_fma(w[j + 1] * r1, r1, sse);
+  } else if (rem == 1) {
+    const double d0 = phf_hill_den(model, lc[j], hill, ln_ic50, k_exp);
+    PHF_SHARE_PUT_(j, d0);
+    const double r = y[j] - PHF_PCT_(phf_rcp(d0));
+    sse = phf_fma(w[j] * r, r, sse);
+  }
+  j = n_other;
+  const int n = n_other + n_cens;
+  for (; j + 2 <= n; j += 2) {
+    const double d0 = PHF_CDEN_(j), d1 = PHF_CDEN_(j + 1);
+    const double inv = phf_rcp(d0 * d1);
+    const double z0 = phf_censored_z(PHF_PCT_(inv * d1), y[j], inv_s);
+    const double z1 = phf_censored_z(PHF_PCT_(inv * d0), y[j + 1], inv_s);
+    cens = phf_fma(w[j], phf_log_ndtr_tab(z0, -z0 * PHF_INV_SQRT2), cens);
+    cens = phf_fma(w[j + 1], phf_log_ndtr_tab(z1, -z1 * PHF_INV_SQRT2), cens);
+  }
+  for (; j < n; ++j) {
+    const double pred = PHF_PCT_(phf_rcp(PHF_CDEN_(j)));
+    const double z = phf_censored_z(pred, y[j], inv_s);
+    cens = phf_fma(w[j], phf_log_ndtr_tab(z, -z * PHF_INV_SQRT2), cens);
+  }
+  double a = cens - pi_bit;
+  a = phf_fma(-n_other_points, log_sigma, a);
+  a = phf_fma(-sse, 0.5 * inv_s * inv_s, a);
+  if (sigma <= PHF_SIGMA_FLOOR) a = -PHF_INF;
+  double lik = temperature * a;
+  if (temperature == 0.0) lik = 0.0;
+  *out_lik = lik;
+  *out_ll1 = a;
+
+  const int outside = (pic50 < PHF_PIC50_LOWER)
+                      | (sigma <= PHF_SIGMA_LOC)
+                      | ((model == 2) & ((hill < 0.0) | (hill > PHF_HILL_UPPER)));
+  const double g = phf_fma(PHF_SIGMA_SHAPE_M1, log_sl, -sl * PHF_SIGMA_INV_SCALE);
+  const double lp = -PHF_PIC50_RATE * pic50 + g;
+  *out_prior = outside ? -PHF_INF : lp;
+}
+#undef PHF_SHARE_PUT_
+#undef PHF_CDEN_
+
 /* The random numbers of MH iteration t of one chain — ONE Philox4x32-10 block (128 bits) per iteration:
  *   d == 2: z0, z1 from words 0, 1 (phf_normal_u32: piecewise inverse CDF of a 31-bit uniform + a sign bit, |z| <= 6.34),
  *           accept uniform from words 2, 3 (53 bits: numpy's random_sample construction);

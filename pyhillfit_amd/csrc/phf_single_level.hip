@@ -23,6 +23,8 @@ constexpr int kBlock = 64;
 thread_local int g_last_sl_kernel = 0;        // phf_single_level_last_kernel(): 1 hipcc, 2 gfx950 assembly, 3 gfx950 assembly as a work queue
 constexpr int kQueuePoison = 0x40000000;     // task counter value that makes every wavefront of a queued launch leave
 constexpr int kQueueMaxRounds = 16;          // beyond this many rounds of the chip's wavefront slots the tail of a launch is negligible
+constexpr int kDenSlots = 4;                 // LDS slots [kDenSlots][kBlock] for the uncensored Hill denominators censored entries reuse
+constexpr int kMaxShared = 4;                // censored entries per pair that may reuse one (the straight-line bodies' 0..4)
 
 template <int MODEL> struct Dim { static constexpr int d = (MODEL == 1) ? 2 : 3; };
 
@@ -93,9 +95,15 @@ __device__ __forceinline__ void stage_points(const phf_points& pts, int pair, do
 // KO / KC >= 0: the pair's numbers of uncensored / censored entries are these compile-time constants (the point loops of
 // phf_sl_log_target fold away and an iteration is straight-line code the scheduler can interleave: measured 17 % faster
 // on Amiodarone-hERG); -1: read from the data at run time.  Either way the same operations in the same order.
-template <int MODEL, bool MOMENTS, int KO, int KC, bool LONE_WAVE>
-__device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double* s_pts, int q, int c, int pair,
-                                             int n_other_rt, int n_cens_rt, const int64_t t_begin, const int64_t t_end) {
+// SHARE: the censored entries (bit m = censored entry m) that take their Hill denominator from the uncensored entry at the same
+// ln_conc bits instead of evaluating it again (phf_sl_log_target_shared): each iteration the uncensored entries write their
+// denominators to this wavefront's LDS slots s_den[j][lane] (ds_write2st64_b64: one per two entries), and a shared entry reads slot
+// den_off[m] / kBlock — one ds_read_b64 in place of ~19 VALU, nearly all fp64.  Same doubles, same results.
+template <int MODEL, bool MOMENTS, int KO, int KC, unsigned SHARE, bool LONE_WAVE>
+__device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double* s_pts, double* s_den, const int* den_off, int q,
+                                             int c, int pair, int n_other_rt, int n_cens_rt, const int64_t t_begin, const int64_t t_end) {
+  static_assert(SHARE == 0 || (KO >= 1 && KO <= kDenSlots && KC >= 1 && KC <= kMaxShared && (SHARE >> KC) == 0),
+                "shared denominators need a straight-line body with at most kDenSlots uncensored entries");
   constexpr int D = Dim<MODEL>::d;
   constexpr int NTRI = D * (D + 1) / 2;
   const int C = a.prob.chains_per_problem;
@@ -177,7 +185,8 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
     }
     // ---- target and accept test (PyHillFit.py:833-838) ----
     double lik_star, prior_star, ll1_star;
-    phf_sl_log_target(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature, star, k_exp, k_log, &lik_star, &prior_star, &ll1_star);
+    phf_sl_log_target_shared(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature, star, k_exp, k_log,
+                             SHARE, den_off, s_den + threadIdx.x, kBlock, &lik_star, &prior_star, &ll1_star);
     const double lt_star = lik_star + prior_star;
     const bool acc = log_u < lt_star - lt;
     if (acc) {
@@ -254,17 +263,43 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
   }
 }
 
-// Entry-count shapes with a straight-line body: 1..4 uncensored x 0..4 censored entries = 203 of the 210 Crumb pairs
-// (the set has 4 nominal doses per pair); anything else runs the run-time loops.  The moment-accumulating builds (what the
-// command lines and the thermodynamic-integration path run) have the same bodies: with the run-time loops a wavefront that has
-// its SIMD to itself — 64 chains per pair — was 25 % slower (C2 shape: 4.34 ms against 3.27).
-#define PHF_SHAPE_CASE(ko, kc) \
-  case (ko) * 8 + (kc): advance_body<MODEL, MOMENTS, ko, kc, WPS == 1>(a, s_pts, q, c, pair, n_other, n_cens, t_begin, t_end); break;
+// Entry-count shapes with a straight-line body: 0..5 uncensored x 0..4 censored entries = all 210 Crumb pairs (the set has 4 nominal
+// doses per pair); anything else runs the run-time loops.  The moment-accumulating builds (what the command lines and the
+// thermodynamic-integration path run) have the same bodies: with the run-time loops a wavefront that has its SIMD to itself — 64
+// chains per pair — was 25 % slower (C2 shape: 4.34 ms against 3.27).
+// Shapes whose censored entries commonly sit at a dose that also has an uncensored entry have a second body, with those entries'
+// Hill denominators shared (SHARE, advance_body): the masks below are the ones the Crumb pairs have (two pairs or more; 141 of the
+// 210 pairs run one, sharing 290 of the 310 shareable censored entries).  A pair runs it when its censored entries include the
+// mask's (sharing fewer entries than it could is still the same arithmetic); every other pair runs the no-sharing body of its shape.
+#define PHF_BODY_(ko, kc, sh) \
+  advance_body<MODEL, MOMENTS, ko, kc, sh, WPS == 1>(a, s_pts, s_den, den_off, q, c, pair, n_other, n_cens, t_begin, t_end)
+#define PHF_SHAPE_CASE(ko, kc) case (ko) * 8 + (kc): PHF_BODY_(ko, kc, 0u); break;
+#define PHF_SHAPE_CASE_SHARED(ko, kc, sh) \
+  case (ko) * 8 + (kc): if ((share & (sh)) == (sh)) PHF_BODY_(ko, kc, sh); else PHF_BODY_(ko, kc, 0u); break;
 #define PHF_SHAPE_ROW(ko) PHF_SHAPE_CASE(ko, 0) PHF_SHAPE_CASE(ko, 1) PHF_SHAPE_CASE(ko, 2) PHF_SHAPE_CASE(ko, 3) PHF_SHAPE_CASE(ko, 4)
+
+// Bit m set: censored entry m has the ln_conc bits of an uncensored entry j < kDenSlots, and den_off[m] = j * kBlock (the first
+// such j).  Bits, not values: dose 0 (ln_conc -inf) matches itself, and no two different doubles are confused.  Wave-uniform.
+__device__ __forceinline__ unsigned share_map(const double* s_pts, int n_other, int n_cens, int* den_off) {
+  unsigned share = 0;
+#pragma unroll
+  for (int m = 0; m < kMaxShared; ++m) {
+    den_off[m] = 0;
+    if (m < n_cens && n_other <= kDenSlots) {
+      const long long b = __double_as_longlong(s_pts[n_other + m]);
+#pragma unroll
+      for (int j = kDenSlots - 1; j >= 0; --j)
+        if (j < n_other && __double_as_longlong(s_pts[j]) == b) { share |= 1u << m; den_off[m] = j * kBlock; }
+    }
+    den_off[m] = __builtin_amdgcn_readfirstlane(den_off[m]);
+  }
+  return __builtin_amdgcn_readfirstlane(share);
+}
 
 // One block (= one wavefront = 64 chains of one problem) from iteration t_begin to t_end: state in, samples out, state out.
 template <int MODEL, bool MOMENTS, int WPS>
-__device__ __forceinline__ void run_block(const AdvanceArgs& a, double* s_pts, int block, const int64_t t_begin, const int64_t t_end) {
+__device__ __forceinline__ void run_block(const AdvanceArgs& a, double* s_pts, double* s_den, int block, const int64_t t_begin,
+                                          const int64_t t_end) {
   const int slot = block / a.blocks_per_problem;
   const int chunk = block - slot * a.blocks_per_problem;
   const int q = a.prob.launch_order ? a.prob.launch_order[slot] : slot;     // which problem this wavefront works on (wave-uniform)
@@ -274,14 +309,24 @@ __device__ __forceinline__ void run_block(const AdvanceArgs& a, double* s_pts, i
   stage_points(a.pts, pair, s_pts, n_other, n_zero, n_hundred);
   if (c >= a.prob.chains_per_problem) return;
   const int n_cens = n_zero + n_hundred;
-  if (n_other <= 4 && n_cens <= 4) {
+  int den_off[kMaxShared];
+  const unsigned share = share_map(s_pts, n_other, n_cens, den_off);
+  if (n_other <= 5 && n_cens <= 4) {
     switch (n_other * 8 + n_cens) {                     // wave-uniform
-      PHF_SHAPE_ROW(1) PHF_SHAPE_ROW(2) PHF_SHAPE_ROW(3) PHF_SHAPE_ROW(4)
-      default: advance_body<MODEL, MOMENTS, -1, -1, WPS == 1>(a, s_pts, q, c, pair, n_other, n_cens, t_begin, t_end); break;
+      PHF_SHAPE_CASE(0, 1) PHF_SHAPE_CASE(0, 2) PHF_SHAPE_CASE(0, 3) PHF_SHAPE_CASE(0, 4)
+      PHF_SHAPE_CASE(1, 0) PHF_SHAPE_CASE(1, 1) PHF_SHAPE_CASE(1, 2) PHF_SHAPE_CASE(1, 3) PHF_SHAPE_CASE_SHARED(1, 4, 0x8u)
+      PHF_SHAPE_CASE(2, 0) PHF_SHAPE_CASE_SHARED(2, 1, 0x1u) PHF_SHAPE_CASE_SHARED(2, 2, 0x3u) PHF_SHAPE_CASE_SHARED(2, 3, 0x4u)
+      PHF_SHAPE_CASE_SHARED(2, 4, 0xcu)
+      PHF_SHAPE_CASE(3, 0) PHF_SHAPE_CASE(3, 1) PHF_SHAPE_CASE_SHARED(3, 2, 0x2u) PHF_SHAPE_CASE_SHARED(3, 3, 0x6u)
+      PHF_SHAPE_CASE_SHARED(3, 4, 0xeu)
+      PHF_SHAPE_CASE(4, 0) PHF_SHAPE_CASE_SHARED(4, 1, 0x1u) PHF_SHAPE_CASE_SHARED(4, 2, 0x3u) PHF_SHAPE_CASE_SHARED(4, 3, 0x7u)
+      PHF_SHAPE_CASE_SHARED(4, 4, 0xfu)
+      PHF_SHAPE_ROW(5)
+      default: PHF_BODY_(-1, -1, 0u); break;
     }
     return;
   }
-  advance_body<MODEL, MOMENTS, -1, -1, WPS == 1>(a, s_pts, q, c, pair, n_other, n_cens, t_begin, t_end);
+  PHF_BODY_(-1, -1, 0u);
 }
 
 // WPS = wavefronts per SIMD the register allocation allows for: 2 (256 registers) for launches that fill the chip more than
@@ -304,6 +349,7 @@ __global__ __launch_bounds__(kBlock, WPS) void mh_advance_kernel(const AdvanceAr
   PHF_NORMAL_TABLE_TO_LDS();
   PHF_LOGPHI_TABLE_TO_LDS();
   extern __shared__ double s_pts[];
+  __shared__ double s_den[kDenSlots * kBlock];                   // 2 KiB: shared Hill denominators (advance_body), one slot row per entry
   const bool queued = a.queue != nullptr;                         // wave-uniform; ONE call site of run_block serves both kinds of launch
   const int nblocks = a.blocks_per_problem * a.prob.num_problems;
   const int total = queued ? nblocks * (int)((a.t_end - a.t_begin + a.quantum - 1) / a.quantum) : 0;
@@ -339,7 +385,7 @@ __global__ __launch_bounds__(kBlock, WPS) void mh_advance_kernel(const AdvanceAr
       t0 = a.t_begin + (int64_t)k * a.quantum;
       t1 = (t0 + a.quantum < a.t_end) ? t0 + a.quantum : a.t_end;
     }
-    run_block<MODEL, MOMENTS, WPS>(a, s_pts, b, t0, t1);
+    run_block<MODEL, MOMENTS, WPS>(a, s_pts, s_den, b, t0, t1);
     if (!queued) break;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");           // every lane: its part of this block's state (and rows) is in HBM ...
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -41,9 +41,13 @@ def issue_cycles(line):
     return 4
 
 
-# pairs of the Crumb set per (uncensored entries, censored entries) after merging replicates (pyhillfit_amd.doseresponse.pack_single_level)
-SHAPE_WEIGHTS = [((4, 1), 45), ((4, 0), 41), ((4, 2), 25), ((4, 4), 22), ((4, 3), 13), ((3, 4), 11), ((2, 4), 9), ((3, 3), 7), ((1, 4), 6),
-                 ((2, 3), 5), ((2, 2), 5), ((3, 2), 4), ((3, 1), 3), ((1, 3), 3), ((2, 1), 3), ((2, 0), 1)]
+# pairs of the Crumb set per (uncensored entries, censored entries, runs the shared-denominator body of its shape) after merging
+# replicates (pyhillfit_amd.doseresponse.pack_single_level; the masks the kernel offers: phf_single_level.hip, run_block).  A listing
+# without shared-denominator bodies counts a shape's sharing pairs on its plain body.
+SHAPE_WEIGHTS = [((4, 1, 1), 45), ((4, 0, 0), 41), ((4, 2, 1), 25), ((4, 4, 1), 22), ((4, 3, 1), 13), ((3, 4, 1), 9), ((3, 4, 0), 2),
+                 ((3, 3, 1), 6), ((3, 3, 0), 1), ((2, 4, 1), 6), ((2, 4, 0), 3), ((1, 4, 1), 3), ((1, 4, 0), 3), ((2, 3, 1), 3),
+                 ((2, 3, 0), 2), ((2, 2, 1), 2), ((2, 2, 0), 3), ((3, 2, 1), 4), ((3, 1, 0), 3), ((1, 3, 0), 3), ((2, 1, 1), 3),
+                 ((2, 0, 0), 1), ((0, 4, 0), 3), ((0, 2, 0), 1), ((5, 0, 0), 2), ((5, 1, 0), 1)]
 
 
 def main():
@@ -103,32 +107,51 @@ def main():
             c["(issue cycles)"] = cyc
             rows.append((valu, fp, a, b, c))
         # which entry-count shape a body is (single-level kernels): LDS reads = 13 + uncensored entries + 6 x censored entries
-        # (one 2^(j/64) read per entry; five 16-byte reads of the log Phi table per censored entry; 13 for the draws and the logarithms)
-        weights = dict(SHAPE_WEIGHTS) if len(sys.argv) > 3 and sys.argv[3] == "crumb" else {}
-        tot, wsum = collections.Counter(), 0
-        cyc_tot = collections.Counter()
+        # (one 2^(j/64) read per entry; five 16-byte reads of the log Phi table per censored entry; 13 for the draws and the logarithms;
+        # a censored entry that shares its Hill denominator reads it from its LDS slot instead of the 2^(j/64) table), and LDS writes
+        # (the uncensored entries' denominators to their slots) only in the shared-denominator bodies
+        shapes = {}
+        for valu, fp, a, b, c in rows:
+            reads = sum(1 for l in ins[a:b + 1] if l.startswith("ds_read"))
+            shared = int(any(l.startswith("ds_write") for l in ins[a:b + 1]))
+            shapes[a] = next(((ko, kc, shared) for ko in range(0, 6) for kc in range(0, 5) if 13 + ko + 6 * kc == reads), None)
+        weights = {}
+        if len(sys.argv) > 3 and sys.argv[3] == "crumb":
+            have = set(shapes.values())
+            for (ko, kc, sh), n in SHAPE_WEIGHTS:
+                key = (ko, kc, sh) if (ko, kc, sh) in have else (ko, kc, 0)
+                weights[key] = weights.get(key, 0) + n
+        averages = [("", lambda s_: True, {}, {}, [0]),
+                    (" of the shapes 1..4 uncensored x 0..4 censored", lambda s_: 1 <= s_[0] <= 4, {}, {}, [0])]
         for valu, fp, a, b, c in sorted(rows, key=lambda r: r[:4]):
             cyc = c.pop("(issue cycles)")
-            lds = c.get("(not VALU) LDS", 0)
-            shape = next(((ko, kc) for ko in range(1, 5) for kc in range(0, 5) if 13 + ko + 6 * kc == lds), None)
+            shape = shapes[a]
             w = weights.get(shape, 0)
             print("\n  body [%d..%d]%s: %d instructions, %d VALU of which %d fp64 fma / mul / add" % (
-                a, b, "" if shape is None else " = %d uncensored + %d censored entries (%d of the 210 Crumb pairs)" % (shape[0], shape[1], w), b - a + 1, valu, fp))
+                a, b, "" if shape is None else " = %d uncensored + %d censored entries%s (%d of the 210 Crumb pairs)" % (
+                    shape[0], shape[1], ", shared denominators" if shape[2] else "", w), b - a + 1, valu, fp))
             for k_, v in sorted(c.items(), key=lambda kv: (kv[0].startswith("(not VALU)"), -kv[1])):
                 print("     %5d  %s" % (v, k_))
-                tot[k_] += v * w
             print("     issue cycles of the vector pipe per wavefront: %d = %s" % (sum(cyc.values()), ", ".join("%d %s" % (v, k_) for k_, v in cyc.most_common())))
-            for k_, v in cyc.items():
-                cyc_tot[k_] += v * w
-            wsum += w
-        if wsum:
-            print("\n  AVERAGE over the %d Crumb pairs whose shape has a straight-line body (weights = pairs per shape):" % wsum)
+            for _, keep, tot, cyc_tot, wsum in averages:
+                if shape is None or not keep(shape):
+                    continue
+                for k_, v in c.items():
+                    tot[k_] = tot.get(k_, 0) + v * w
+                for k_, v in cyc.items():
+                    cyc_tot[k_] = cyc_tot.get(k_, 0) + v * w
+                wsum[0] += w
+        for what, _, tot, cyc_tot, wsum in averages:
+            wsum = wsum[0]
+            if not wsum:
+                continue
+            print("\n  AVERAGE over the %d Crumb pairs%s whose shape has a straight-line body (weights = pairs per body):" % (wsum, what))
             valu = sum(v for k_, v in tot.items() if not k_.startswith("(not VALU)")) / wsum
             print("     %7.1f  VALU in all" % valu)
             for k_, v in sorted(tot.items(), key=lambda kv: (kv[0].startswith("(not VALU)"), -kv[1])):
                 print("     %7.1f  %s" % (v / wsum, k_))
             print("     issue cycles of the vector pipe per wavefront and iteration (measured cost per instruction: tools/isa_instr_cost.py): %.0f" % (sum(cyc_tot.values()) / wsum))
-            for k_, v in cyc_tot.most_common():
+            for k_, v in sorted(cyc_tot.items(), key=lambda kv: -kv[1]):
                 print("     %7.0f  %s" % (v / wsum, k_))
 
 
