@@ -443,6 +443,47 @@ int phf_waic_accumulate(const phf_pointwise_points* pts, int likelihood, int num
 int phf_waic_reduce(int num_problems, int stride, int num_chains, int64_t total_rows, const double* workspace, size_t workspace_bytes,
                     double* out, void* stream);
 
+/* ---- PSIS-LOO ----------------------------------------------------------------------------------------------------------------
+ * Pareto-smoothed importance-sampling leave-one-out (Vehtari, Simpson, Gelman, Yao & Gabry, JMLR 2024; r_eff = 1) of every data point,
+ * streamed like WAIC (pyhillfit_amd/csrc/phf_psis.hip; DESIGN.md §3, "PSIS-LOO").  Points, likelihoods and rows as phf_waic_*: the
+ * same pointwise log-likelihood l.  Over the S = total_rows x num_chains draws of a point, with r = -l:
+ *   M = ceil(min(S/5, 3 sqrt S)) (phf_psis_tail_length); the tail = the M smallest l, the cutoff = the (M+1)-th smallest;
+ *   a generalised Pareto fit to the tail's exceedances exp(r) - exp(r_cutoff) (shifted by max r) by Zhang & Stephens (2009) with
+ *   30 + floor(sqrt M) grid points, k-hat <- (M k-hat + 5)/(M + 10); the tail's ratios replaced by rank with the quantiles at
+ *   (j - 1/2)/M, capped at the largest raw ratio; every weight truncated at S^(3/4) x the mean weight;
+ *   elpd_loo_i = ln sum w exp(l) - ln sum w, lppd_i = ln mean exp(l).
+ * Edge cases: M < 5 — no fit, k-hat = +inf, sigma-hat = NaN, the raw ratios truncated; a tail whose exceedances are all equal —
+ * nothing to smooth, k-hat = 0, sigma-hat = 0; a draw with l = -inf (sigma <= 1e-3) — elpd_loo_i = -inf, k-hat = +inf, sigma-hat = NaN.
+ *   tail_per_chain  k, the heap capacity per (point, chain), capped at min(M + 1, total_rows); 0: the default, k = min(M + 1,
+ *                   total_rows) — every point exact by construction — whenever that workspace stays within 32 GiB, else
+ *                   2 ceil((M + 1)/num_chains) + 32 (phf_psis_tail_per_chain returns the k in use).  k x num_chains (k x total_rows
+ *                   if fewer) must reach M + 1.  A draw at or above the point's bound T on the cutoff (the bucket of the (M+1)-th smallest
+ *                   value held by all heaps together, to 1/16 of a binade, recomputed after every 1024th row up to row 8192, then every 8192nd)
+ *                   goes straight to the non-tail sum.
+ *   workspace       device, phf_psis_workspace_bytes(...): [num_problems][stride][6][num_chains] doubles (a running max and sum of
+ *                   exp(-l - max) over the draws not in the heap, the same of +l over all draws, the heap's fill count, the heap
+ *                   insertions so far), then [num_problems][stride] doubles (T), then [num_problems][stride][k][num_chains]
+ *                   doubles (a max-heap of the chain's k smallest l), then, when M + 1 > 8192, the reduce's sort scratch;
+ *                   phf_psis_init zeroes the counts and sets T = +inf (stream-ordered)
+ *   out             device [5][num_problems][stride]: elpd_loo_i, lppd_i, k-hat_i, sigma-hat_i, determined_i (1 or 0); valid once all
+ *                   total_rows rows have arrived; NaN (determined 0) beyond a problem's count
+ *   tail_out        NULL, or device [num_problems][stride][M + 1]: the M + 1 smallest l of each point, ascending
+ * Exactness: the values a chain did not keep are all >= its final heap maximum, so the selection is exact unless some chain has a
+ * full heap (that dropped draws) whose maximum lies below the cutoff: that point is NOT DETERMINED and written NaN, determined = 0.
+ * Deterministic: no atomics in the accumulation, every accumulator produced by one lane in row order; the reduce selects by exact
+ * integer counts and merges the chains in a fixed order.  Bit-identical however the rows are cut into calls.  An invalid shape gives
+ * 0 / PHF_ERR_INVALID_ARGUMENT without touching a GPU (phf_last_error() says why). */
+int64_t phf_psis_tail_length(int num_chains, int64_t total_rows);
+int phf_psis_tail_per_chain(int num_problems, int stride, int num_chains, int64_t total_rows, int tail_per_chain);
+size_t phf_psis_workspace_bytes(int num_problems, int stride, int num_chains, int64_t total_rows, int tail_per_chain);
+int phf_psis_init(int num_problems, int stride, int num_chains, int64_t total_rows, int tail_per_chain, double* workspace,
+                  size_t workspace_bytes, void* stream);
+int phf_psis_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
+                        int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, int tail_per_chain,
+                        double* workspace, size_t workspace_bytes, void* stream);
+int phf_psis_reduce(const phf_pointwise_points* pts, int num_problems, int num_chains, int64_t total_rows, int tail_per_chain,
+                    double* workspace, size_t workspace_bytes, double* out, double* tail_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
     python -m pyhillfit_amd.PyHillFit --data-file ../data/crumb_data.csv -m 2 -a [--hierarchical]
            [-i 500000] [-t 5] [-b 4] [-c N] [-Ne 0] [--num-APs 500] [-bfo]
            [--num-chains 64 | 128 with --hierarchical] [--seed 25] [--device cuda:0] [--save-all-chains] [--segment 20000]
-           [--diagnostics [--diagnostic-lags 256]] [--waic]
+           [--diagnostics [--diagnostic-lags 256]] [--waic] [--loo [--loo-tail-per-chain 0]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -12,7 +12,8 @@ pair (burn-in removed exactly like PyHillFit.py:861-864); with --save-all-chains
 `<chain file minus .txt>_all_chains.npy` ([rows][d+1][chains]); posterior moments of all chains, accumulated on the
 device, go to `<...>_summary.json`; with --diagnostics, also split-R-hat / ESS / MCSE of every column over all chains
 (pyhillfit_amd/diagnostics.py), accumulated on the device segment by segment; with --waic, WAIC and the pointwise predictive
-accuracy of every data point over all chains (pyhillfit_amd/waic.py), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
+accuracy of every data point over all chains (pyhillfit_amd/waic.py), accumulated the same way; with --loo, PSIS-LOO and the Pareto
+k-hat of every data point (pyhillfit_amd/loo.py), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -65,6 +66,11 @@ def build_parser():
     new.add_argument("--diagnostic-lags", type=int, default=256, help="lag limit K of the autocorrelation sums of --diagnostics")
     new.add_argument("--waic", action='store_true', default=False, help="WAIC, p_waic and the pointwise elpd of every data point over all "
                      "chains' post-burn-in draws, accumulated on the GPU while the rows stream past; written to the summary JSON as \"waic\"")
+    new.add_argument("--loo", action='store_true', default=False, help="PSIS-LOO: elpd_loo, p_loo and the Pareto k-hat of every data point over "
+                     "all chains' post-burn-in draws, accumulated on the GPU while the rows stream past; written to the summary JSON as \"loo\"")
+    new.add_argument("--loo-tail-per-chain", type=int, default=0, help="--loo: smallest log-likelihoods kept per (point, chain); 0: "
+                     "M + 1 for the tail length M (every point exact) while the workspace fits 32 GiB, else 2 ceil((M + 1)/chains) + 32.  "
+                     "Raise it if points are reported undetermined")
     new.add_argument("--fused-launch", choices=["auto", "on", "off"], default="auto",
                      help="--hierarchical: the launch groups the gfx950 code object has kernels for (Ne = 3; Ne = 4 with 4 + 4 + 4 + 1 / 2 / 3 points) through "
                           "ONE persistent grid per segment instead of a launch each (auto: when the run's chains give every SIMD a wavefront); same numbers")
@@ -159,6 +165,15 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         waic = wc.PointwiseWAIC(wpts, model, Q, C, saved_iterations - burn, device)
         if burn == 0:
             waic.accumulate(s.row0.unsqueeze(0).contiguous())
+    psis = None
+    if getattr(args, "loo", False):
+        from . import loo as lo
+        from . import waic as wc
+        lpts = wc.Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))
+        lo.check_memory(lo.workspace_bytes(Q, lpts.stride, C, saved_iterations - burn, args.loo_tail_per_chain), device)
+        psis = lo.PointwiseLOO(lpts, model, Q, C, saved_iterations - burn, device, args.loo_tail_per_chain)
+        if burn == 0:
+            psis.accumulate(s.row0.unsqueeze(0).contiguous())
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
             chainio.host_buffer((saved_iterations, Q, d + 1, 1)))   # pinned: chain 0 leaves the GPU asynchronously
     kept[0] = s.row0 if keep_all else s.row0[:, :, :1].cpu()
@@ -176,6 +191,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             diag.accumulate(rows[first:])
         if waic is not None and first < nr:
             waic.accumulate(rows[first:])
+        if psis is not None and first < nr:
+            psis.accumulate(rows[first:])
         # stream-ordered and asynchronous: the next segment is queued behind this copy while the host moves on (a blocking copy
         # here left the GPU idle for the gather + transfer + launch latency of every segment)
         kept[r:r + nr].copy_(rows if keep_all else rows[:, :, :, :1], non_blocking=True)
@@ -187,6 +204,9 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     acc = s.acceptance().cpu().numpy()
     diag_res = diag.result() if diag is not None else None
     waic_res = waic.result() if waic is not None else None
+    loo_res = psis.result() if psis is not None else None
+    if psis is not None:
+        psis.free()
     summaries = []
     for q, (d_clean, c_clean, chain_file) in enumerate(files):
         chain0 = kept[:, q, :, 0].cpu().numpy()
@@ -205,6 +225,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             summ["diagnostics"] = dg.json_record(diag_res, q, args.diagnostic_lags, saved_iterations - burn, C)
         if waic_res is not None:
             summ["waic"] = wc.json_record(waic_res[q], wpts, q)
+        if loo_res is not None:
+            summ["loo"] = lo.json_record(loo_res[q], lpts, q, psis.M, psis.k)
         with open(chain_file[:-4] + "_summary.json", "w") as f:
             json.dump(summ, f, indent=1)
         summaries.append(summ)
@@ -214,6 +236,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         print(dg.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], diag_res["rhat"], diag_res["ess"]))
     if waic_res is not None:
         print(wc.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], waic_res))
+    if loo_res is not None:
+        print(lo.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], loo_res))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, Q * C, total_iterations, time.time() - start - elapsed))
     return summaries

@@ -1,8 +1,10 @@
-"""Compare fits by WAIC: the elpd difference of every two summaries and its pointwise standard error (Vehtari, Gelman & Gabry 2017).
+"""Compare fits by WAIC or PSIS-LOO: the elpd difference of every two summaries and its pointwise standard error (Vehtari, Gelman &
+Gabry 2017).
 
-    python -m pyhillfit_amd.compare_models SUMMARY_A SUMMARY_B [...] [--intersection]
+    python -m pyhillfit_amd.compare_models SUMMARY_A SUMMARY_B [...] [--intersection] [--criterion {waic,loo}]
 
-Each argument is a `<chain>_summary.json` written with --waic, or an output directory searched for them.  The summaries of each
+Each argument is a `<chain>_summary.json` written with --waic (--criterion waic, the default) or --loo (--criterion loo), or an
+output directory searched for them.  The summaries of each
 argument are keyed by (drug, channel); for every two arguments A, B (in the order given) and every pair both hold:
 
     elpd_diff = sum_i (elpd_A,i - elpd_B,i),  se_diff = sqrt(n var_i(elpd_A,i - elpd_B,i)),  preferred: A if elpd_diff > 2 se_diff,
@@ -12,7 +14,9 @@ Points are aligned by (experiment, dose, response) (replicates in order of appea
 (an error entry) unless --intersection asks for the common points.  Points where one fit has a censored MASS (single-level,
 y == 0 or 100) and the other a DENSITY (uncensored or the hierarchical truncated normal) are compared all the same but counted as
 "mixed": their log-likelihoods are not on one scale.  Model 1 against model 2 has none; single-level against hierarchical has one per
-censored point.  One JSON object on stdout, then a table on stderr."""
+censored point.  With --criterion loo the pointwise elpd_loo are compared; a pair where either fit has a common point with Pareto
+k-hat above its threshold is marked ("khat_flagged": its difference rests on unreliable points), and a pair where either fit has a
+point without an elpd_loo (not determined, or -inf) is refused.  One JSON object on stdout, then a table on stderr."""
 import argparse
 import glob
 import json
@@ -24,18 +28,18 @@ import numpy as np
 CENSORED = ("censored-0", "censored-100")
 
 
-def load_sources(path):
-    """{(drug, channel): summary} of a summary file or of every summary under a directory"""
+def load_sources(path, criterion="waic"):
+    """{(drug, channel): summary} of a summary file or of every summary under a directory (those with a `criterion` object)"""
     files = [path] if os.path.isfile(path) else sorted(glob.glob(os.path.join(path, "**", "*_summary.json"), recursive=True))
     out = {}
     for f in files:
         with open(f) as fh:
             s = json.load(fh)
-        if "waic" not in s:
+        if criterion not in s:
             continue
         out[(s["drug"], s["channel"])] = dict(s, _file=f)
     if not out:
-        raise SystemExit("%s: no summary with a \"waic\" object (run with --waic)" % path)
+        raise SystemExit("%s: no summary with a \"%s\" object (run with --%s)" % (path, criterion, criterion))
     return out
 
 
@@ -50,8 +54,9 @@ def _keys(w):
     return keys
 
 
-def compare(wa, wb, intersection=False):
-    """two "waic" objects -> dict of the comparison (or with "error" if the point sets differ and intersection is not asked)"""
+def compare(wa, wb, intersection=False, criterion="waic"):
+    """two "waic" (or, criterion "loo", two "loo") objects -> dict of the comparison (or with "error" if the point sets differ and
+    intersection is not asked, or a loo point has no elpd_loo)"""
     ka, kb = _keys(wa), _keys(wb)
     ia, ib = {k: i for i, k in enumerate(ka)}, {k: i for i, k in enumerate(kb)}
     common = [k for k in ka if k in ib]
@@ -60,8 +65,15 @@ def compare(wa, wb, intersection=False):
     if (only_a or only_b) and not intersection:
         rec["error"] = "point sets differ ({} only in A, {} only in B): use --intersection to compare the common points".format(only_a, only_b)
         return rec
-    ea = np.array([wa["pointwise"]["elpd"][ia[k]] for k in common], dtype=np.float64)
-    eb = np.array([wb["pointwise"]["elpd"][ib[k]] for k in common], dtype=np.float64)
+    field = "elpd_loo" if criterion == "loo" else "elpd"
+    if criterion == "loo":
+        missing = [sum(1 for k in common if w["pointwise"]["elpd_loo"][i[k]] is None) for w, i in ((wa, ia), (wb, ib))]
+        if any(missing):
+            rec["error"] = ("points without an elpd_loo (not determined: raise --loo-tail-per-chain; or -inf): {} in A, {} in B"
+                            .format(*missing))
+            return rec
+    ea = np.array([wa["pointwise"][field][ia[k]] for k in common], dtype=np.float64)
+    eb = np.array([wb["pointwise"][field][ib[k]] for k in common], dtype=np.float64)
     kind_a = [wa["points"]["kind"][ia[k]] for k in common]
     kind_b = [wb["points"]["kind"][ib[k]] for k in common]
     mixed = [(x in CENSORED) != (y in CENSORED) for x, y in zip(kind_a, kind_b)]
@@ -72,6 +84,12 @@ def compare(wa, wb, intersection=False):
     pref = "A" if diff > 2 * se else "B" if diff < -2 * se else "neither"
     rec.update({"elpd_a": float(np.sum(ea)), "elpd_b": float(np.sum(eb)), "elpd_diff": diff, "se_diff": se, "preferred": pref,
                 "n_mixed": int(sum(mixed))})
+    if criterion == "loo":
+        ka_ = [wa["pointwise"]["khat"][ia[k]] for k in common]
+        kb_ = [wb["pointwise"]["khat"][ib[k]] for k in common]
+        na = sum(1 for v in ka_ if v is None or v > wa["khat_threshold"])   # null: an infinite k-hat
+        nb = sum(1 for v in kb_ if v is None or v > wb["khat_threshold"])
+        rec.update({"n_khat_a": na, "n_khat_b": nb, "khat_flagged": bool(na or nb)})
     if any(mixed):
         rec["warning"] = ("{} points are a censored probability mass in one fit and a density in the other: their elpd are not "
                           "commensurable".format(int(sum(mixed))))
@@ -82,20 +100,22 @@ def _num(v):
     return None if v is None or not np.isfinite(v) else v
 
 
-def compare_sources(sources, names, intersection=False):
+def compare_sources(sources, names, intersection=False, criterion="waic"):
     out = []
     for i in range(len(sources)):
         for j in range(i + 1, len(sources)):
             for key in [k for k in sources[i] if k in sources[j]]:
                 sa, sb = sources[i][key], sources[j][key]
-                rec = compare(sa["waic"], sb["waic"], intersection)
+                rec = compare(sa[criterion], sb[criterion], intersection, criterion)
                 rec = {k: (_num(v) if isinstance(v, float) else v) for k, v in rec.items()}
                 out.append(dict({"drug": key[0], "channel": key[1], "a": names[i], "b": names[j], "file_a": sa["_file"],
                                  "file_b": sb["_file"]}, **rec))
     return out
 
 
-def table(rows):
+def table(rows, criterion="waic"):
+    if criterion == "loo":
+        return _loo_table(rows)
     lines = ["{:<28} {:>10} {:>8} {:>8} {:>6} {:>7}".format("pair (A vs B)", "elpd_diff", "se", "pref.", "n", "mixed")]
     for r in rows:
         name = "{} + {}".format(r["drug"], r["channel"])
@@ -107,17 +127,32 @@ def table(rows):
     return "\n".join(lines)
 
 
+def _loo_table(rows):
+    lines = ["{:<28} {:>10} {:>8} {:>8} {:>6} {:>7} {:>9}".format("pair (A vs B)", "elpd_diff", "se", "pref.", "n", "mixed", "k>thr A/B")]
+    for r in rows:
+        name = "{} + {}".format(r["drug"], r["channel"])
+        if "error" in r:
+            lines.append("{:<28} {}".format(name, r["error"]))
+            continue
+        lines.append("{:<28} {:>10.2f} {:>8.2f} {:>8} {:>6} {:>7} {:>9}".format(
+            name, r["elpd_diff"], r["se_diff"] if r["se_diff"] is not None else float("nan"), r["preferred"], r["n_points"],
+            r["n_mixed"], "{}/{}".format(r["n_khat_a"], r["n_khat_b"])))
+    return "\n".join(lines)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="compare_models")
-    ap.add_argument("summaries", nargs="+", help="<chain>_summary.json files written with --waic, or output directories")
+    ap.add_argument("summaries", nargs="+", help="<chain>_summary.json files written with --waic / --loo, or output directories")
     ap.add_argument("--intersection", action="store_true", help="compare the points two fits share when their point sets differ")
+    ap.add_argument("--criterion", choices=["waic", "loo"], default="waic",
+                    help="compare the pointwise elpd of WAIC (default) or of PSIS-LOO (summaries written with --loo)")
     a = ap.parse_args(argv)
     if len(a.summaries) < 2:
         raise SystemExit("compare_models needs at least two summaries or directories")
-    rows = compare_sources([load_sources(p) for p in a.summaries], a.summaries, a.intersection)
+    rows = compare_sources([load_sources(p, a.criterion) for p in a.summaries], a.summaries, a.intersection, a.criterion)
     print(json.dumps({"comparisons": rows}))
     sys.stdout.flush()
-    print(table(rows), file=sys.stderr)
+    print(table(rows, a.criterion), file=sys.stderr)
     return rows
 
 

@@ -476,6 +476,10 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     writers = chainio.WriterPool(getattr(args, "write_workers", 0))    # one pool for the start-point fits and the file formatting
     chain_streams = chainio.StreamWriters(getattr(args, "write_workers", 0))   # the chain files, written segment by segment
     # one sampler and one HIP stream per Ne group: the groups are independent, their launches overlap on the GPU
+    if getattr(args, "loo", False):                                    # every group's PSIS-LOO workspace together, before any is made
+        from . import loo as lo
+        lo.check_memory(sum(lo.workspace_bytes(len(m), max(sum(len(x) for x in it[2]) for it in m), args.num_chains,
+                                               saved_iterations - burn, args.loo_tail_per_chain) for m in groups.values()), device)
     runs = []
     ordered = sorted(groups.items(), reverse=True)
     # all start points first, in one sweep over the worker pool (the file-writer processes start after it)
@@ -521,8 +525,18 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             waic = wc.PointwiseWAIC(wpts, "hierarchical", Q, C, saved_iterations - burn, device)
             if burn == 0:
                 waic.accumulate(s.row0.unsqueeze(0).contiguous())
+        psis = None
+        if getattr(args, "loo", False):                                # PSIS-LOO over all chains, accumulated like WAIC
+            from . import loo as lo
+            from . import waic as wc
+            from .PyHillFit import experiments_and_labels
+            lpts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
+            lo.check_memory(lo.workspace_bytes(Q, lpts.stride, C, saved_iterations - burn, args.loo_tail_per_chain), device)
+            psis = lo.PointwiseLOO(lpts, "hierarchical", Q, C, saved_iterations - burn, device, args.loo_tail_per_chain)
+            if burn == 0:
+                psis.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, waic=waic, stream=torch.cuda.Stream(device=device)))
+                         diag=diag, waic=waic, psis=psis, stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
     fused = None
@@ -575,6 +589,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     run["diag"].accumulate(rows[first:])
                 if run["waic"] is not None and first < nr:
                     run["waic"].accumulate(rows[first:])
+                if run["psis"] is not None and first < nr:
+                    run["psis"].accumulate(rows[first:])
                 run["kept"][run["r"]:run["r"] + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # chain 0 of each pair
                 ev = torch.cuda.Event()
                 ev.record(run["stream"])
@@ -593,6 +609,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     total_chains = sum(len(r_["members"]) for r_ in runs) * args.num_chains
     diag_names, diag_parts = [], []
     waic_names, waic_parts = [], []
+    loo_names, loo_parts = [], []
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
         Q, C = len(members), args.num_chains
@@ -603,6 +620,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         if diag_res is not None:
             run["diag"].free()
         waic_res = run["waic"].result() if run["waic"] is not None else None
+        loo_res = run["psis"].result() if run["psis"] is not None else None
+        if loo_res is not None:
+            run["psis"].free()
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
@@ -626,6 +646,11 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                 summ["waic"] = wc.json_record(waic_res[q], run["waic"].points, q)
                 waic_names.append("{} + {}".format(d_clean, c_clean))
                 waic_parts.append(waic_res[q])
+            if loo_res is not None:
+                from . import loo as lo
+                summ["loo"] = lo.json_record(loo_res[q], run["psis"].points, q, run["psis"].M, run["psis"].k)
+                loo_names.append("{} + {}".format(d_clean, c_clean))
+                loo_parts.append(loo_res[q])
             with open(chain_file[:-4] + "_summary.json", "w") as f:
                 json.dump(summ, f, indent=1)
             summaries.append(summ)
@@ -636,6 +661,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     if getattr(args, "waic", False):
         from . import waic as wc
         print(wc.report_line(rank, waic_names, waic_parts))
+    if getattr(args, "loo", False):
+        from . import loo as lo
+        print(lo.report_line(rank, loo_names, loo_parts))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, total_chains, total_iterations, time.time() - start - elapsed))
     return summaries
