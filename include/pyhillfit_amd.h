@@ -484,6 +484,39 @@ int phf_psis_accumulate(const phf_pointwise_points* pts, int likelihood, int num
 int phf_psis_reduce(const phf_pointwise_points* pts, int num_problems, int num_chains, int64_t total_rows, int tail_per_chain,
                     double* workspace, size_t workspace_bytes, double* out, double* tail_out, void* stream);
 
+/* ---- posterior quantiles and curve bands -------------------------------------------------------------------------------------
+ * Exact-count histograms of every (problem, column) over all chains' draws, streamed like the diagnostics
+ * (pyhillfit_amd/csrc/phf_quantiles.hip; DESIGN.md §3, "Posterior quantiles").  A workspace holds S = num_problems x (num_columns +
+ * curve_points) slots; slot q (num_columns + curve_points) + c is column c of problem q's rows (c < num_columns) or the Hill curve
+ * of problem q at dose c - num_columns.  Per slot: B = bins bins (a power of two in [64, 32768]), an anchor a (the first finite
+ * value in (row, chain) order of all rows accumulated), w0 = 2^(floor(log2 max(|a|, 2^-30)) - 40) and a level k; a value x falls
+ * in bin j = floor(((x - a) * (1/w0)) * 2^-k) + B/2, k being the least level whose bins hold the slot's [min, max].  So the counts
+ * are those of binning every draw at the final grid, the same however the rows are cut into calls, and unless k = 0 a bin is at
+ * most 4 (max - min) / B wide.  Values that are not finite (or lie beyond ~2^980 w0 of a) are counted apart, never binned.
+ *   rows        device [num_rows][num_problems][row_stride_cols][num_chains] (the layout phf_diagnostics_accumulate reads);
+ *               num_rows x num_chains < 2^31 per call; calls in row order, [first_row, first_row + num_rows) within total_rows
+ *   ln_doses    curves: device [num_problems][curve_points], the natural log of each dose; the curve of model 1 | 2 is
+ *               100 (1 - 1/(1 + exp(Hill (ln c - ln IC50)))) with pIC50 = column 0 and Hill = column 1 (model 2) or 1
+ *   workspace   device, phf_quantiles_workspace_bytes(...): uint64 counts [S][bins], then double [S][8] (a, w0, min, max, level,
+ *               anchored, 0, 0), then uint64 [S] non-finite counts; phf_quantiles_init zeroes it (stream-ordered)
+ *   probs       HOST array of num_probs (1 to 64) probabilities in [0, 1]
+ *   out         device [S][8 + 4 num_probs]: min, max, finite draws N, non-finite draws, bin width w0 2^k, k, a, w0; then per p the
+ *               value (linear in rank inside the bin), the bin's edges lo, hi (clamped to [min, max]) and the bin index, for the
+ *               rank r = ceil(p N) draw (clamped to [1, N]: numpy's quantile(method="inverted_cdf")); NaN where N = 0
+ * Deterministic: integer counts (uint32 in LDS, uint64 atomics in HBM).  An invalid shape gives 0 bytes / PHF_ERR_INVALID_ARGUMENT
+ * without touching a GPU (phf_last_error() says why). */
+size_t phf_quantiles_workspace_bytes(int num_problems, int num_columns, int curve_points, int bins);
+int phf_quantiles_init(int num_problems, int num_columns, int curve_points, int bins, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int phf_quantiles_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                             int num_columns, int curve_points, int bins, int64_t first_row, int64_t total_rows, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int phf_quantiles_accumulate_curves(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                                    int model, const double* ln_doses, int num_columns, int curve_points, int bins, int64_t first_row,
+                                    int64_t total_rows, void* workspace, size_t workspace_bytes, void* stream);
+int phf_quantiles_reduce(int num_problems, int num_columns, int curve_points, int bins, const double* probs, int num_probs,
+                         const void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
            [-i 500000] [-t 5] [-b 4] [-c N] [-Ne 0] [--num-APs 500] [-bfo]
            [--num-chains 64 | 128 with --hierarchical] [--seed 25] [--device cuda:0] [--save-all-chains] [--segment 20000]
            [--diagnostics [--diagnostic-lags 256]] [--waic] [--loo [--loo-tail-per-chain 0]]
+           [--quantiles [--quantile-probs 0.025,...,0.975] [--quantile-bins 16384] [--curve-bands G]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -13,7 +14,9 @@ pair (burn-in removed exactly like PyHillFit.py:861-864); with --save-all-chains
 device, go to `<...>_summary.json`; with --diagnostics, also split-R-hat / ESS / MCSE of every column over all chains
 (pyhillfit_amd/diagnostics.py), accumulated on the device segment by segment; with --waic, WAIC and the pointwise predictive
 accuracy of every data point over all chains (pyhillfit_amd/waic.py), accumulated the same way; with --loo, PSIS-LOO and the Pareto
-k-hat of every data point (pyhillfit_amd/loo.py), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
+k-hat of every data point (pyhillfit_amd/loo.py), accumulated the same way; with --quantiles, posterior quantiles and 90 / 95 %
+credible intervals of every column over all chains (pyhillfit_amd/quantiles.py), and with --curve-bands G the same of the
+dose-response curve at G doses, accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -31,6 +34,36 @@ import numpy as np
 from . import bestfit, chainio
 from . import distributed as phfdist
 from . import doseresponse as dr
+
+
+QUANTILE_PROBS = (0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975)
+
+
+def _probs(text):
+    from .quantiles import parse_probs
+    try:
+        return parse_probs(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _bins(text):
+    b = int(text)
+    if b < 64 or b > 32768 or b & (b - 1):
+        raise argparse.ArgumentTypeError("must be a power of two in [64, 32768], got %d" % b)
+    return b
+
+
+def check_args(parser, args):
+    """refusals that need no GPU"""
+    if isinstance(args.quantile_probs, str):
+        args.quantile_probs = _probs(args.quantile_probs)
+    if args.curve_bands < 0:
+        parser.error("--curve-bands must be >= 0")
+    if args.curve_bands and args.hierarchical:
+        parser.error("--curve-bands is single-level only (no bands for the hierarchical model)")
+    if args.curve_bands and not args.quantiles:
+        parser.error("--curve-bands needs --quantiles")
 
 
 def build_parser():
@@ -71,6 +104,16 @@ def build_parser():
     new.add_argument("--loo-tail-per-chain", type=int, default=0, help="--loo: smallest log-likelihoods kept per (point, chain); 0: "
                      "M + 1 for the tail length M (every point exact) while the workspace fits 32 GiB, else 2 ceil((M + 1)/chains) + 32.  "
                      "Raise it if points are reported undetermined")
+    new.add_argument("--quantiles", action='store_true', default=False, help="posterior quantiles of every column over all chains' "
+                     "post-burn-in draws (each reported with the bracket that holds the exact sample quantile) and the central 90 %% and "
+                     "95 %% credible intervals, from histograms accumulated on the GPU while the rows stream past; written to the summary "
+                     "JSON as \"quantiles\"")
+    new.add_argument("--quantile-probs", type=_probs, default=",".join(str(p) for p in QUANTILE_PROBS),
+                     help="--quantiles: the probabilities, comma-separated")
+    new.add_argument("--quantile-bins", type=_bins, default=16384, help="--quantiles: histogram bins per column, a power of two")
+    new.add_argument("--curve-bands", type=int, default=0, metavar="G", help="--quantiles, single-level only: also the quantiles of the "
+                     "dose-response curve at G doses log-spaced from the pair's smallest dose / 10 to its largest x 10; written to the "
+                     "summary JSON as \"curve_band\"")
     new.add_argument("--fused-launch", choices=["auto", "on", "off"], default="auto",
                      help="--hierarchical: the launch groups the gfx950 code object has kernels for (Ne = 3; Ne = 4 with 4 + 4 + 4 + 1 / 2 / 3 points) through "
                           "ONE persistent grid per segment instead of a launch each (auto: when the run's chains give every SIMD a wavefront); same numbers")
@@ -174,6 +217,16 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         psis = lo.PointwiseLOO(lpts, model, Q, C, saved_iterations - burn, device, args.loo_tail_per_chain)
         if burn == 0:
             psis.accumulate(s.row0.unsqueeze(0).contiguous())
+    quant, doses = None, None
+    if getattr(args, "quantiles", False):
+        from . import quantiles as qn
+        G = getattr(args, "curve_bands", 0)
+        doses = [qn.curve_doses(concs, G) for _, _, concs, _ in loaded] if G else None
+        qn.check_memory(qn.workspace_bytes(Q, d + 1, G, args.quantile_bins), device)
+        quant = qn.PosteriorQuantiles(Q, C, d + 1, saved_iterations - burn, args.quantile_probs, args.quantile_bins, device,
+                                      curve_ln_doses=np.log(np.array(doses)) if G else None, model=model)
+        if burn == 0:
+            quant.accumulate(s.row0.unsqueeze(0).contiguous())
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
             chainio.host_buffer((saved_iterations, Q, d + 1, 1)))   # pinned: chain 0 leaves the GPU asynchronously
     kept[0] = s.row0 if keep_all else s.row0[:, :, :1].cpu()
@@ -193,6 +246,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             waic.accumulate(rows[first:])
         if psis is not None and first < nr:
             psis.accumulate(rows[first:])
+        if quant is not None and first < nr:
+            quant.accumulate(rows[first:])
         # stream-ordered and asynchronous: the next segment is queued behind this copy while the host moves on (a blocking copy
         # here left the GPU idle for the gather + transfer + launch latency of every segment)
         kept[r:r + nr].copy_(rows if keep_all else rows[:, :, :, :1], non_blocking=True)
@@ -207,6 +262,9 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     loo_res = psis.result() if psis is not None else None
     if psis is not None:
         psis.free()
+    quant_res = quant.result() if quant is not None else None
+    if quant is not None:
+        quant.free()
     summaries = []
     for q, (d_clean, c_clean, chain_file) in enumerate(files):
         chain0 = kept[:, q, :, 0].cpu().numpy()
@@ -227,6 +285,10 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             summ["waic"] = wc.json_record(waic_res[q], wpts, q)
         if loo_res is not None:
             summ["loo"] = lo.json_record(loo_res[q], lpts, q, psis.M, psis.k)
+        if quant_res is not None:
+            summ["quantiles"] = qn.json_record(quant_res, q, dr.file_labels + ["log-target"], args.quantile_bins)
+            if doses is not None:
+                summ["curve_band"] = qn.curve_band_record(quant_res, q, doses[q])
         with open(chain_file[:-4] + "_summary.json", "w") as f:
             json.dump(summ, f, indent=1)
         summaries.append(summ)
@@ -238,6 +300,11 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         print(wc.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], waic_res))
     if loo_res is not None:
         print(lo.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], loo_res))
+    if quant_res is not None:
+        n = d + 1
+        print(qn.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files],
+                             [(quant_res["bin_width"][q, :n], quant_res["min"][q, :n], quant_res["max"][q, :n], quant_res["non_finite"][q, :n])
+                              for q in range(len(files))]))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, Q * C, total_iterations, time.time() - start - elapsed))
     return summaries
@@ -264,6 +331,7 @@ def main(argv=None):
         parser.print_help()
         sys.exit(1)
     args = parser.parse_args(argv)
+    check_args(parser, args)
     n = phfdist.ranks_for_cores(args.num_cores)                        # -c N: the reference's pool (PyHillFit.py:997-1003) -> N ranks
     if n:
         sys.exit(phfdist.spawn_ranks("pyhillfit_amd.PyHillFit", sys.argv[1:] if argv is None else argv, n))

@@ -1,0 +1,472 @@
+// phf_quantiles.hip — posterior quantiles and dose-response credible bands from exact-count histograms (include/pyhillfit_amd.h).
+//
+// Per slot (problem, column) — a column of the rows, or one dose of the Hill curve (curve bands) — the workspace keeps B bins of a
+// grid fixed by an anchor a (the first finite value, in (row, chain) order, of all rows accumulated), a power-of-two base width
+// w0 = 2^(floor(log2 max(|a|, 2^-30)) - 40) and a level k:
+//     t = (x - a) * (1/w0)          (1/w0 is a power of two: the same double as (x - a)/w0; -ffp-contract=off: no FMA anywhere)
+//     j = floor(t * 2^-k) + B/2     (t * 2^-k by ldexp: exact)
+// Each accumulate call runs
+//   prepare  one workgroup per slot: the anchor (first call with a finite value), a min/max pass over the call's values, then the
+//            least level k' >= k whose bins hold the running [min, max]; when k' > k the counts merge 2^(k'-k)-fold in place
+//            (floor(floor(y)/2^m) = floor(y/2^m): the final counts are those of binning every value at the final level, which is
+//            the least level holding the global [min, max] — the same however the rows are cut into calls);
+//   bin      workgroups of (slot, slice of the call's values): a workgroup-private uint32 histogram in LDS (a wavefront whose lanes
+//            all fall in one bin adds once), flushed to the uint64 counts in HBM with integer atomics for its non-zero bins only.
+// Integer counts are order-independent: the result is bit-identical whatever the launch shape, the arrival order or the row cuts.
+// A value that is not finite, or whose t is not (|x - a| beyond ~2^980 w0), is counted apart and never binned.
+// reduce: one workgroup per slot, a prefix sum over the bins; for each p the bin of the rank r = ceil(p N) draw (clamped to [1, N];
+// numpy's quantile(method="inverted_cdf")), its edges clamped to [min, max], and a value interpolated linearly by rank in the bin.
+#include <hip/hip_runtime.h>
+
+#include "../../include/pyhillfit_amd.h"
+#include "phf_common.h"
+#include "phf_pointwise.h"
+
+namespace {
+
+constexpr int kPrepThreads = 256;
+constexpr int kBinThreads = 512;
+constexpr int kReduceThreads = 256;
+constexpr int kHdr = 8;                 // anchor, w0, min, max, level, anchored, 0, 0
+constexpr int kOutHead = 8;             // min, max, finite draws, non-finite, bin width, level, anchor, w0
+constexpr int kOutPerProb = 4;          // value, lo, hi, bin
+constexpr int kMinBins = 64, kMaxBins = 32768, kMaxProbs = 64;
+constexpr int64_t kValuesPerBlock = 131072;   // values one bin workgroup takes before a call's slot is split over more
+constexpr int kTargetBlocks = 4096;           // ... up to about this many bin workgroups per launch
+constexpr int64_t kMaxFlat = 0x7fffffff;      // rows x chains of one call: a 31-bit flat index
+
+struct QArgs {
+  const double* rows;             // [nr][Q][stride][C]
+  const double* ln_dose;          // curves: [Q][G]
+  unsigned n;                     // nr * C values per slot in this call
+  int Q, stride, C, B, G;
+  int spp;                        // slots per problem: columns + curve points
+  int first, count;               // this launch's slot columns [first, first + count) of every problem
+  int splits;
+  unsigned per_split;
+  unsigned long long* counts;     // [S][B]
+  double* hdr;                    // [S][kHdr]
+  unsigned long long* nonfinite;  // [S]
+};
+
+struct QReduceArgs {
+  int B, S, P;
+  double probs[kMaxProbs];
+  const unsigned long long* counts;
+  const double* hdr;
+  const unsigned long long* nonfinite;
+  double* out;                    // [S][kOutHead + kOutPerProb P]
+};
+
+// value i (= row * C + chain) of launch column k of problem q: a column of the rows (MODEL 0) or the Hill curve of model MODEL at dose k
+template <int MODEL>
+__device__ inline double q_value(const QArgs& a, int q, int k, unsigned i, phf_ktab k_exp) {
+  const unsigned r = i / (unsigned)a.C, c = i - r * (unsigned)a.C;
+  const double* x = a.rows + ((size_t)r * a.Q + q) * a.stride * (size_t)a.C + c;
+  if (MODEL == 0) return x[(size_t)(a.first + k) * a.C];
+  const double pic50 = x[0], hill = MODEL == 2 ? x[a.C] : 1.0;
+  if (!__builtin_isfinite(pic50) || !__builtin_isfinite(hill)) return PHF_NAN;
+  return phf_pw_pred(MODEL, a.ln_dose[(size_t)q * a.G + k], hill, PHF_LN10 * (6.0 - pic50), k_exp);
+}
+
+__device__ inline double q_t(double x, double anchor, double inv_w0) { return (x - anchor) * inv_w0; }
+
+// do the level-k bins hold [tmin, tmax]?
+__device__ inline bool q_holds(double tmin, double tmax, int k, int B) {
+  return __builtin_floor(__builtin_ldexp(tmin, -k)) >= -(double)(B / 2) && __builtin_floor(__builtin_ldexp(tmax, -k)) < (double)(B / 2);
+}
+
+// the 2^(j/64) table of phf_exp_* into LDS (the Hill curve needs no other table)
+__device__ inline void load_exp_table() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  for (int i = threadIdx.x; i < 64; i += blockDim.x) phf_lds_exp2[i] = phf_t_exp2[i];
+  __syncthreads();
+#endif
+}
+
+// block reductions through a small LDS array (blockDim.x <= 1024: 16 wavefronts)
+__device__ inline double block_min(double v, double* sh) {
+  for (int o = 32; o > 0; o >>= 1) v = __builtin_fmin(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x / 64] = v;
+  __syncthreads();
+  double r = sh[0];
+  for (int w = 1; w < (int)blockDim.x / 64; ++w) r = __builtin_fmin(r, sh[w]);
+  return r;
+}
+
+__device__ inline double block_max(double v, double* sh) { return -block_min(-v, sh); }
+
+__device__ inline unsigned block_min_u(unsigned v, unsigned* sh) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned u = __shfl_xor(v, o, 64);
+    v = u < v ? u : v;
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x / 64] = v;
+  __syncthreads();
+  unsigned r = sh[0];
+  for (int w = 1; w < (int)blockDim.x / 64; ++w) r = sh[w] < r ? sh[w] : r;
+  return r;
+}
+
+// ---- prepare: anchor, min/max, level, merge ----------------------------------------------------------------------------------------
+template <int MODEL>
+__global__ __launch_bounds__(kPrepThreads) void q_prepare_kernel(const QArgs a) {
+  extern __shared__ unsigned long long s_merge[];              // [B/2]
+  __shared__ double s_red[16];
+  __shared__ unsigned s_redu[16];
+  __shared__ int s_level[2];
+  if (MODEL != 0) load_exp_table();
+  PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
+  const int q = blockIdx.x / a.count, k = blockIdx.x % a.count;
+  const size_t s = (size_t)q * a.spp + a.first + k;
+  double* h = a.hdr + s * kHdr;
+  const int tid = threadIdx.x;
+  if (h[5] == 0.0) {                                           // not anchored yet: the first finite value in (row, chain) order
+    unsigned best = 0xffffffffu;
+    for (unsigned i = tid; i < a.n; i += kPrepThreads)
+      if (__builtin_isfinite(q_value<MODEL>(a, q, k, i, k_exp))) { best = i; break; }
+    best = block_min_u(best, s_redu);
+    if (best == 0xffffffffu) return;                           // nothing finite yet: the bin pass counts every value apart
+    if (tid == 0) {
+      const double x = q_value<MODEL>(a, q, k, best, k_exp);
+      const double m = __builtin_fmax(__builtin_fabs(x), 0x1p-30);
+      h[0] = x;
+      h[1] = __builtin_ldexp(1.0, __builtin_amdgcn_frexp_exp(m) - 41);   // frexp exponent - 1 = floor(log2 m)
+      h[2] = x; h[3] = x; h[4] = 0.0; h[5] = 1.0;
+    }
+    __syncthreads();
+  }
+  const double anchor = h[0], inv_w0 = 1.0 / h[1];             // a power of two: exact
+  double lo = PHF_INF, hi = -PHF_INF;
+  for (unsigned i = tid; i < a.n; i += kPrepThreads) {
+    const double x = q_value<MODEL>(a, q, k, i, k_exp);
+    if (__builtin_isfinite(q_t(x, anchor, inv_w0))) { lo = __builtin_fmin(lo, x); hi = __builtin_fmax(hi, x); }
+  }
+  lo = block_min(lo, s_red);
+  hi = block_max(hi, s_red);
+  if (tid == 0) {
+    const double mn = __builtin_fmin(h[2], lo), mx = __builtin_fmax(h[3], hi);
+    const int k0 = (int)h[4];
+    int k1 = k0;
+    const double tmin = q_t(mn, anchor, inv_w0), tmax = q_t(mx, anchor, inv_w0);
+    while (!q_holds(tmin, tmax, k1, a.B) && k1 < 1100) ++k1;
+    h[2] = mn; h[3] = mx; h[4] = (double)k1;
+    s_level[0] = k0; s_level[1] = k1;
+  }
+  __syncthreads();
+  const int k0 = s_level[0], k1 = s_level[1];
+  if (k1 == k0) return;
+  // merge: new bin of old j = ((j - B/2) >> D) + B/2 (an arithmetic shift is floor division); D >= log2 B acts as log2 B
+  int log2B = 0;
+  while ((1 << log2B) < a.B) ++log2B;
+  const int D = k1 - k0 < log2B ? k1 - k0 : log2B;
+  const int half = a.B / 2;
+  const int nlo = half + ((-half) >> D), nn = half + ((half - 1) >> D) - nlo + 1;   // nn <= B/2
+  for (int i = tid; i < nn; i += kPrepThreads) s_merge[i] = 0ull;
+  __syncthreads();
+  unsigned long long* cnt = a.counts + s * a.B;
+  for (int j = tid; j < a.B; j += kPrepThreads) {
+    const unsigned long long c = cnt[j];
+    if (c) atomicAdd(&s_merge[((j - half) >> D) + half - nlo], c);
+  }
+  __syncthreads();
+  for (int j = tid; j < a.B; j += kPrepThreads) cnt[j] = (j >= nlo && j < nlo + nn) ? s_merge[j - nlo] : 0ull;
+}
+
+// ---- bin: LDS histogram per workgroup, flushed with integer atomics ----------------------------------------------------------------
+template <int MODEL>
+__global__ __launch_bounds__(kBinThreads) void q_bin_kernel(const QArgs a) {
+  extern __shared__ unsigned s_hist[];                          // [B]
+  if (MODEL != 0) load_exp_table();
+  PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
+  const int split = blockIdx.x % a.splits;
+  const int slot = blockIdx.x / a.splits;
+  const int q = slot / a.count, k = slot % a.count;
+  const size_t s = (size_t)q * a.spp + a.first + k;
+  const double* h = a.hdr + s * kHdr;
+  const bool anchored = h[5] != 0.0;
+  const double anchor = h[0], inv_w0 = 1.0 / h[1];
+  const int level = (int)h[4], half = a.B / 2;
+  const int tid = threadIdx.x;
+  for (int j = tid; j < a.B; j += kBinThreads) s_hist[j] = 0u;
+  __syncthreads();
+  const unsigned i0 = (unsigned)split * a.per_split;
+  const unsigned i1 = i0 >= a.n ? i0 : (a.n - i0 < a.per_split ? a.n : i0 + a.per_split);   // [i0, i1) within [0, n)
+  unsigned nf = 0;
+  const int lane = __lane_id();
+  for (unsigned i = i0 + tid; i < i1; i += kBinThreads) {
+    const double x = q_value<MODEL>(a, q, k, i, k_exp);
+    int j = -1;
+    if (anchored) {
+      const double t = q_t(x, anchor, inv_w0);
+      if (__builtin_isfinite(t)) {
+        const double f = __builtin_floor(__builtin_ldexp(t, -level)) + (double)half;
+        j = (int)__builtin_fmin(__builtin_fmax(f, 0.0), (double)(a.B - 1));   // the level holds [min, max]: the clamp is a guard
+      }
+    }
+    nf += j < 0;
+    const unsigned long long active = __ballot(1);
+    const int j0 = __builtin_amdgcn_readfirstlane(j);
+    if (__ballot(j != j0) == 0) {                                // the whole wavefront in one bin (a stuck or constant column)
+      if (j0 >= 0 && lane == __ffsll((long long)active) - 1) atomicAdd(&s_hist[j0], (unsigned)__popcll(active));
+    } else if (j >= 0) {
+      atomicAdd(&s_hist[j], 1u);
+    }
+  }
+  __syncthreads();
+  unsigned long long* cnt = a.counts + s * a.B;
+  for (int j = tid; j < a.B; j += kBinThreads) {
+    const unsigned c = s_hist[j];
+    if (c) atomicAdd(&cnt[j], (unsigned long long)c);
+  }
+  if (nf) atomicAdd(&a.nonfinite[s], (unsigned long long)nf);
+}
+
+// ---- reduce ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kReduceThreads) void q_reduce_kernel(const QReduceArgs a) {
+  __shared__ unsigned long long s_sum[kReduceThreads];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const unsigned long long* cnt = a.counts + (size_t)s * a.B;
+  const double* h = a.hdr + (size_t)s * kHdr;
+  double* o = a.out + (size_t)s * (kOutHead + kOutPerProb * a.P);
+  const int chunk = a.B / kReduceThreads > 0 ? a.B / kReduceThreads : 1;
+  const int used = a.B / chunk;                                 // threads holding a chunk of the bins
+  unsigned long long mine = 0;
+  if (tid < used)
+    for (int j = tid * chunk; j < (tid + 1) * chunk; ++j) mine += cnt[j];
+  s_sum[tid] = mine;
+  __syncthreads();
+  if (tid == 0) {                                               // exclusive prefix sum of the chunks, in order
+    unsigned long long run = 0;
+    for (int t = 0; t < kReduceThreads; ++t) {
+      const unsigned long long v = s_sum[t];
+      s_sum[t] = run;
+      run += v;
+    }
+    const bool anchored = h[5] != 0.0;
+    o[0] = anchored ? h[2] : PHF_NAN;
+    o[1] = anchored ? h[3] : PHF_NAN;
+    o[2] = (double)run;
+    o[3] = (double)a.nonfinite[s];
+    o[4] = anchored ? __builtin_ldexp(h[1], (int)h[4]) : PHF_NAN;
+    o[5] = h[4];
+    o[6] = anchored ? h[0] : PHF_NAN;
+    o[7] = anchored ? h[1] : PHF_NAN;
+    for (int p = 0; p < a.P; ++p)
+      for (int f = 0; f < kOutPerProb; ++f) o[kOutHead + kOutPerProb * p + f] = PHF_NAN;
+  }
+  __syncthreads();
+  const unsigned long long before = s_sum[tid];
+  const double N = o[2];
+  if (N == 0.0 || tid >= used) return;
+  const double mn = h[2], mx = h[3], width = __builtin_ldexp(h[1], (int)h[4]), anchor = h[0];
+  const int half = a.B / 2;
+  for (int p = 0; p < a.P; ++p) {
+    double r = __builtin_ceil(a.probs[p] * N);
+    r = __builtin_fmin(__builtin_fmax(r, 1.0), N);
+    const unsigned long long rank = (unsigned long long)r;
+    if (!(before < rank && rank <= before + mine)) continue;   // exactly one thread holds the rank-r draw
+    unsigned long long cum = before;
+    int j = tid * chunk;
+    for (; j < (tid + 1) * chunk - 1; ++j) {
+      if (cum + cnt[j] >= rank) break;
+      cum += cnt[j];
+    }
+    const double e = (double)(j - half) * width;                // exact: a small integer times a power of two
+    double lo = __builtin_fmax(anchor + e, mn), hi = __builtin_fmin(anchor + (e + width), mx);
+    lo = __builtin_fmin(lo, hi);
+    const double nb = (double)cnt[j];
+    const double v = lo + (hi - lo) * (((double)(rank - cum) - 0.5) / nb);
+    double* op = o + kOutHead + kOutPerProb * p;
+    op[0] = v; op[1] = lo; op[2] = hi; op[3] = (double)j;
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+struct Layout {
+  size_t slots, counts_bytes, hdr_bytes, nf_bytes;
+  size_t total() const { return counts_bytes + hdr_bytes + nf_bytes; }
+};
+
+Layout layout_of(int num_problems, int num_columns, int curve_points, int bins) {
+  Layout l;
+  l.slots = (size_t)num_problems * (size_t)(num_columns + curve_points);
+  l.counts_bytes = l.slots * (size_t)bins * 8;
+  l.hdr_bytes = l.slots * kHdr * 8;
+  l.nf_bytes = l.slots * 8;
+  return l;
+}
+
+int check_geometry(const char* who, int num_problems, int num_columns, int curve_points, int bins) {
+  char msg[kPhfErrorBufferSize];
+  if (num_problems < 1 || num_columns < 0 || curve_points < 0 || num_columns + curve_points < 1) {
+    std::snprintf(msg, sizeof msg, "%s: num_problems must be positive, num_columns and curve_points non-negative, not both 0", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (bins < kMinBins || bins > kMaxBins || (bins & (bins - 1)) != 0) {
+    std::snprintf(msg, sizeof msg, "%s: bins must be a power of two in [%d, %d] (got %d)", who, kMinBins, kMaxBins, bins);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if ((double)num_problems * (num_columns + curve_points) > 2147483647.0 / 8) {
+    std::snprintf(msg, sizeof msg, "%s: too many slots (fewer problems per workspace)", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  return PHF_OK;
+}
+
+int check_workspace(const char* who, const void* ws, size_t bytes, const Layout& l) {
+  char msg[kPhfErrorBufferSize];
+  if (!ws) {
+    std::snprintf(msg, sizeof msg, "%s: null workspace", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (bytes < l.total()) {
+    std::snprintf(msg, sizeof msg, "%s: workspace smaller than phf_quantiles_workspace_bytes()", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  return PHF_OK;
+}
+
+int check_rows(const char* who, const double* rows, int64_t num_rows, int row_stride_cols, int num_chains, int needed_cols,
+               int64_t first_row, int64_t total_rows) {
+  char msg[kPhfErrorBufferSize];
+  if (num_chains < 1 || row_stride_cols < 1) {
+    std::snprintf(msg, sizeof msg, "%s: num_chains and row_stride_cols must be positive", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (row_stride_cols < needed_cols) {
+    std::snprintf(msg, sizeof msg, "%s: row_stride_cols (%d) is smaller than the columns read (%d)", who, row_stride_cols, needed_cols);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (total_rows < 1 || num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows) {
+    std::snprintf(msg, sizeof msg, "%s: rows [first_row, first_row + num_rows) must lie in [0, total_rows)", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if ((double)num_rows * num_chains > (double)kMaxFlat) {
+    std::snprintf(msg, sizeof msg, "%s: num_rows x num_chains must stay below 2^31 per call (accumulate in shorter segments)", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (num_rows > 0 && !rows) {
+    std::snprintf(msg, sizeof msg, "%s: null rows", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  return PHF_OK;
+}
+
+template <typename K>
+int allow_lds(K kernel, size_t bytes, const char* who) {
+  if (bytes <= 65536) return PHF_OK;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return phf_check_launch(who);
+  return PHF_OK;
+}
+
+template <int MODEL>
+int launch(QArgs a, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int slots = a.Q * a.count;
+  const int64_t want = (a.n + kValuesPerBlock - 1) / kValuesPerBlock;
+  const int64_t room = kTargetBlocks / slots > 1 ? kTargetBlocks / slots : 1;
+  a.splits = (int)(want < room ? (want > 0 ? want : 1) : room);
+  a.per_split = (unsigned)((a.n + a.splits - 1) / a.splits);
+  const size_t merge_lds = (size_t)a.B / 2 * 8, hist_lds = (size_t)a.B * 4;
+  int rc;
+  if ((rc = allow_lds(q_prepare_kernel<MODEL>, merge_lds, "hipFuncSetAttribute(q_prepare_kernel)")) != PHF_OK) return rc;
+  if ((rc = allow_lds(q_bin_kernel<MODEL>, hist_lds, "hipFuncSetAttribute(q_bin_kernel)")) != PHF_OK) return rc;
+  hipLaunchKernelGGL(q_prepare_kernel<MODEL>, dim3(slots), dim3(kPrepThreads), merge_lds, st, a);
+  if ((rc = phf_check_launch("q_prepare_kernel")) != PHF_OK) return rc;
+  hipLaunchKernelGGL(q_bin_kernel<MODEL>, dim3((unsigned)slots * a.splits), dim3(kBinThreads), hist_lds, st, a);
+  return phf_check_launch("q_bin_kernel");
+}
+
+QArgs args_of(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains, int num_columns,
+              int curve_points, int bins, void* workspace) {
+  const Layout l = layout_of(num_problems, num_columns, curve_points, bins);
+  QArgs a = {};
+  a.rows = rows; a.n = (unsigned)(num_rows * num_chains);
+  a.Q = num_problems; a.stride = row_stride_cols; a.C = num_chains; a.B = bins; a.G = curve_points;
+  a.spp = num_columns + curve_points;
+  char* base = static_cast<char*>(workspace);
+  a.counts = reinterpret_cast<unsigned long long*>(base);
+  a.hdr = reinterpret_cast<double*>(base + l.counts_bytes);
+  a.nonfinite = reinterpret_cast<unsigned long long*>(base + l.counts_bytes + l.hdr_bytes);
+  return a;
+}
+
+}  // namespace
+
+extern "C" size_t phf_quantiles_workspace_bytes(int num_problems, int num_columns, int curve_points, int bins) {
+  if (check_geometry("phf_quantiles_workspace_bytes", num_problems, num_columns, curve_points, bins) != PHF_OK) return 0;
+  return layout_of(num_problems, num_columns, curve_points, bins).total();
+}
+
+extern "C" int phf_quantiles_init(int num_problems, int num_columns, int curve_points, int bins, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  static const char* who = "phf_quantiles_init";
+  int rc = check_geometry(who, num_problems, num_columns, curve_points, bins);
+  if (rc != PHF_OK) return rc;
+  const Layout l = layout_of(num_problems, num_columns, curve_points, bins);
+  if ((rc = check_workspace(who, workspace, workspace_bytes, l)) != PHF_OK) return rc;
+  if ((rc = phf_require_device_memory(workspace, "phf_quantiles_init: workspace")) != PHF_OK) return rc;
+  if (hipMemsetAsync(workspace, 0, l.total(), static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch(who);
+  return PHF_OK;
+}
+
+extern "C" int phf_quantiles_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                                        int num_columns, int curve_points, int bins, int64_t first_row, int64_t total_rows,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "phf_quantiles_accumulate";
+  int rc = check_geometry(who, num_problems, num_columns, curve_points, bins);
+  if (rc != PHF_OK) return rc;
+  if (num_columns < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate: the workspace has no columns");
+  if ((rc = check_rows(who, rows, num_rows, row_stride_cols, num_chains, num_columns, first_row, total_rows)) != PHF_OK) return rc;
+  if ((rc = check_workspace(who, workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins))) != PHF_OK) return rc;
+  if (num_rows == 0) return PHF_OK;
+  QArgs a = args_of(rows, num_rows, num_problems, row_stride_cols, num_chains, num_columns, curve_points, bins, workspace);
+  a.first = 0; a.count = num_columns;
+  return launch<0>(a, stream);
+}
+
+extern "C" int phf_quantiles_accumulate_curves(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols,
+                                               int num_chains, int model, const double* ln_doses, int num_columns, int curve_points,
+                                               int bins, int64_t first_row, int64_t total_rows, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  static const char* who = "phf_quantiles_accumulate_curves";
+  int rc = check_geometry(who, num_problems, num_columns, curve_points, bins);
+  if (rc != PHF_OK) return rc;
+  if (model != 1 && model != 2) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_curves: model must be 1 or 2");
+  if (curve_points < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_curves: the workspace has no curve points");
+  if (!ln_doses) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_curves: null ln_doses");
+  if ((rc = check_rows(who, rows, num_rows, row_stride_cols, num_chains, model, first_row, total_rows)) != PHF_OK) return rc;
+  if ((rc = check_workspace(who, workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins))) != PHF_OK) return rc;
+  if (num_rows == 0) return PHF_OK;
+  QArgs a = args_of(rows, num_rows, num_problems, row_stride_cols, num_chains, num_columns, curve_points, bins, workspace);
+  a.ln_dose = ln_doses; a.first = num_columns; a.count = curve_points;
+  return model == 1 ? launch<1>(a, stream) : launch<2>(a, stream);
+}
+
+extern "C" int phf_quantiles_reduce(int num_problems, int num_columns, int curve_points, int bins, const double* probs, int num_probs,
+                                    const void* workspace, size_t workspace_bytes, double* out, void* stream) {
+  static const char* who = "phf_quantiles_reduce";
+  int rc = check_geometry(who, num_problems, num_columns, curve_points, bins);
+  if (rc != PHF_OK) return rc;
+  if (num_probs < 1 || num_probs > kMaxProbs || !probs)
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_reduce: 1 to 64 probabilities, in host memory");
+  for (int p = 0; p < num_probs; ++p)
+    if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_reduce: probabilities must lie in [0, 1]");
+  const Layout l = layout_of(num_problems, num_columns, curve_points, bins);
+  if ((rc = check_workspace(who, workspace, workspace_bytes, l)) != PHF_OK) return rc;
+  if (!out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_reduce: null out");
+  QReduceArgs a = {};
+  a.B = bins; a.S = (int)l.slots; a.P = num_probs;
+  for (int p = 0; p < num_probs; ++p) a.probs[p] = probs[p];
+  const char* base = static_cast<const char*>(workspace);
+  a.counts = reinterpret_cast<const unsigned long long*>(base);
+  a.hdr = reinterpret_cast<const double*>(base + l.counts_bytes);
+  a.nonfinite = reinterpret_cast<const unsigned long long*>(base + l.counts_bytes + l.hdr_bytes);
+  a.out = out;
+  hipLaunchKernelGGL(q_reduce_kernel, dim3((unsigned)l.slots), dim3(kReduceThreads), 0, static_cast<hipStream_t>(stream), a);
+  return phf_check_launch("q_reduce_kernel");
+}

@@ -535,8 +535,15 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             psis = lo.PointwiseLOO(lpts, "hierarchical", Q, C, saved_iterations - burn, device, args.loo_tail_per_chain)
             if burn == 0:
                 psis.accumulate(s.row0.unsqueeze(0).contiguous())
+        quant = None
+        if getattr(args, "quantiles", False):                          # posterior quantiles over all chains, accumulated like the diagnostics
+            from . import quantiles as qn
+            qn.check_memory(qn.workspace_bytes(Q, d + 1, 0, args.quantile_bins), device)
+            quant = qn.PosteriorQuantiles(Q, C, d + 1, saved_iterations - burn, args.quantile_probs, args.quantile_bins, device)
+            if burn == 0:
+                quant.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, waic=waic, psis=psis, stream=torch.cuda.Stream(device=device)))
+                         diag=diag, waic=waic, psis=psis, quant=quant, stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
     fused = None
@@ -591,6 +598,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     run["waic"].accumulate(rows[first:])
                 if run["psis"] is not None and first < nr:
                     run["psis"].accumulate(rows[first:])
+                if run["quant"] is not None and first < nr:
+                    run["quant"].accumulate(rows[first:])
                 run["kept"][run["r"]:run["r"] + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # chain 0 of each pair
                 ev = torch.cuda.Event()
                 ev.record(run["stream"])
@@ -610,6 +619,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     diag_names, diag_parts = [], []
     waic_names, waic_parts = [], []
     loo_names, loo_parts = [], []
+    quant_names, quant_parts = [], []
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
         Q, C = len(members), args.num_chains
@@ -623,6 +633,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         loo_res = run["psis"].result() if run["psis"] is not None else None
         if loo_res is not None:
             run["psis"].free()
+        quant_res = run["quant"].result() if run["quant"] is not None else None
+        if quant_res is not None:
+            run["quant"].free()
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
@@ -651,6 +664,11 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                 summ["loo"] = lo.json_record(loo_res[q], run["psis"].points, q, run["psis"].M, run["psis"].k)
                 loo_names.append("{} + {}".format(d_clean, c_clean))
                 loo_parts.append(loo_res[q])
+            if quant_res is not None:
+                from . import quantiles as qn
+                summ["quantiles"] = qn.json_record(quant_res, q, hierarchical_columns(ne), args.quantile_bins)
+                quant_names.append("{} + {}".format(d_clean, c_clean))
+                quant_parts.append((quant_res["bin_width"][q], quant_res["min"][q], quant_res["max"][q], quant_res["non_finite"][q]))
             with open(chain_file[:-4] + "_summary.json", "w") as f:
                 json.dump(summ, f, indent=1)
             summaries.append(summ)
@@ -664,6 +682,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     if getattr(args, "loo", False):
         from . import loo as lo
         print(lo.report_line(rank, loo_names, loo_parts))
+    if getattr(args, "quantiles", False):
+        from . import quantiles as qn
+        print(qn.report_line(rank, quant_names, quant_parts))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, total_chains, total_iterations, time.time() - start - elapsed))
     return summaries
