@@ -517,6 +517,38 @@ int phf_quantiles_accumulate_curves(const double* rows, int64_t num_rows, int nu
 int phf_quantiles_reduce(int num_problems, int num_columns, int curve_points, int bins, const double* probs, int num_probs,
                          const void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ---- posterior predictive checks ----------------------------------------------------------------------------------------------
+ * (pyhillfit_amd/csrc/phf_ppc.hip, phf_ppc.h; DESIGN.md §3, "Posterior predictive checks").  Points, likelihoods and rows as
+ * phf_waic_*.  Per draw (a row of a chain) and point, one replicated response y_rep:
+ *   single-level   clamp(pred + sigma z, 0, 100), z the generator's normal of one word (|z| <= 6.34);
+ *   hierarchical   the truncated normal on [0, 100] by inversion, pred + sigma ndtri(Phi(a) + u (Phi(b) - Phi(a))), clamped.
+ * Random stream: one Philox block (the samplers' rounds) per (draw, 4 points), counter = (chain_id_base + chain, problem_id[q], row,
+ * 0x80000000 | point block), key = seed: disjoint from every sampler draw (their word 3 is a small block index), independent of how
+ * the rows are cut into calls.  Test quantities T, of y and of y_rep under the same theta, in this order: deviance -2 sum l,
+ * mean, sd (divisor n - 1; 0 for n = 1), #zeros, #hundreds.  A draw with sigma <= 1e-3 (or NaN) is counted invalid and left out.
+ *   problem_id     device [num_problems] uint32: the global problem number of each problem (the samplers' problem_id)
+ *   workspace      device, phf_ppc_workspace_bytes(...) = num_problems * (21 + stride) * num_chains doubles; phf_ppc_init zeroes it
+ *   out            device [num_problems][21 + stride] (sums over all chains): for statistic s, at 4 s + 0..3: #{T(y_rep) > T(y)},
+ *                  #{T(y_rep) = T(y)}, sum T(y_rep), sum T(y); at 20 the number of invalid draws; at 21 + p the sum over the valid
+ *                  draws of P(y_rep < y_p | theta) + P(y_rep = y_p | theta)/2 (the predictive PIT, analytic; 0 beyond count)
+ * At most 512 points per problem (stride).  Deterministic: exact counts, every sum owned by one lane in row order, the chains
+ * merged in a fixed order, no atomics: bit-identical however the rows are cut into calls.  An invalid shape gives 0 bytes /
+ * PHF_ERR_INVALID_ARGUMENT without touching a GPU (phf_last_error() says why). */
+size_t phf_ppc_workspace_bytes(int num_problems, int stride, int num_chains, int64_t total_rows);
+int phf_ppc_init(int num_problems, int stride, int num_chains, int64_t total_rows, double* workspace, size_t workspace_bytes,
+                 void* stream);
+int phf_ppc_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
+                       int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows,
+                       const uint32_t* problem_id, uint32_t chain_id_base, uint64_t seed, double* workspace, size_t workspace_bytes,
+                       void* stream);
+int phf_ppc_reduce(int num_problems, int stride, int num_chains, int64_t total_rows, const double* workspace, size_t workspace_bytes,
+                   double* out, void* stream);
+/* Batch evaluator: vector i of problem problem_index[i] at theta[.][i] ([d][m], as phf_pointwise_loglik_*) with the stream counter
+ * counter[i][0..2] = (chain id, problem id, row) and the key seed: y_rep [m][stride] (NaN beyond the count) and stats [m][2][5]
+ * (T(y), then T(y_rep)); all NaN for an invalid theta or problem index.  Serves the tests and the chain-file tool. */
+int phf_ppc_replicate(const phf_pointwise_points* pts, int likelihood, int num_expts, int64_t m, const int32_t* problem_index,
+                      const double* theta, const uint32_t* counter, uint64_t seed, double* y_rep, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@
            [-i 500000] [-t 5] [-b 4] [-c N] [-Ne 0] [--num-APs 500] [-bfo]
            [--num-chains 64 | 128 with --hierarchical] [--seed 25] [--device cuda:0] [--save-all-chains] [--segment 20000]
            [--diagnostics [--diagnostic-lags 256]] [--waic] [--loo [--loo-tail-per-chain 0]]
-           [--quantiles [--quantile-probs 0.025,...,0.975] [--quantile-bins 16384] [--curve-bands G]]
+           [--quantiles [--quantile-probs 0.025,...,0.975] [--quantile-bins 16384] [--curve-bands G]] [--ppc]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -16,7 +16,8 @@ device, go to `<...>_summary.json`; with --diagnostics, also split-R-hat / ESS /
 accuracy of every data point over all chains (pyhillfit_amd/waic.py), accumulated the same way; with --loo, PSIS-LOO and the Pareto
 k-hat of every data point (pyhillfit_amd/loo.py), accumulated the same way; with --quantiles, posterior quantiles and 90 / 95 %
 credible intervals of every column over all chains (pyhillfit_amd/quantiles.py), and with --curve-bands G the same of the
-dose-response curve at G doses, accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
+dose-response curve at G doses, accumulated the same way; with --ppc, posterior predictive checks (test quantities of replicated
+data against the data, and the predictive PIT of every data point; pyhillfit_amd/ppc.py), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -114,6 +115,9 @@ def build_parser():
     new.add_argument("--curve-bands", type=int, default=0, metavar="G", help="--quantiles, single-level only: also the quantiles of the "
                      "dose-response curve at G doses log-spaced from the pair's smallest dose / 10 to its largest x 10; written to the "
                      "summary JSON as \"curve_band\"")
+    new.add_argument("--ppc", action='store_true', default=False, help="posterior predictive checks: mid-p values of the deviance, mean, sd "
+                     "and counts of 0 and 100 of data replicated from every post-burn-in draw of every chain against the data's, and the "
+                     "predictive PIT of every data point, accumulated on the GPU while the rows stream past; written to the summary JSON as \"ppc\"")
     new.add_argument("--fused-launch", choices=["auto", "on", "off"], default="auto",
                      help="--hierarchical: the launch groups the gfx950 code object has kernels for (Ne = 3; Ne = 4 with 4 + 4 + 4 + 1 / 2 / 3 points) through "
                           "ONE persistent grid per segment instead of a launch each (auto: when the run's chains give every SIMD a wavefront); same numbers")
@@ -227,6 +231,16 @@ def run_single_level(pairs, args, device, rank=0, world=1):
                                       curve_ln_doses=np.log(np.array(doses)) if G else None, model=model)
         if burn == 0:
             quant.accumulate(s.row0.unsqueeze(0).contiguous())
+    ppc = None
+    if getattr(args, "ppc", False):
+        from . import ppc as pp
+        from . import waic as wc
+        ppts = wc.Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))
+        pp.check_memory(pp.workspace_bytes(Q, ppts.stride, C, saved_iterations - burn), device)
+        ppc = pp.PosteriorPredictiveCheck(ppts, model, Q, C, saved_iterations - burn, args.seed,
+                                          [p[4] for p in pairs_with_ids(pairs, loaded)], 0, device)
+        if burn == 0:
+            ppc.accumulate(s.row0.unsqueeze(0).contiguous())
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
             chainio.host_buffer((saved_iterations, Q, d + 1, 1)))   # pinned: chain 0 leaves the GPU asynchronously
     kept[0] = s.row0 if keep_all else s.row0[:, :, :1].cpu()
@@ -248,6 +262,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             psis.accumulate(rows[first:])
         if quant is not None and first < nr:
             quant.accumulate(rows[first:])
+        if ppc is not None and first < nr:
+            ppc.accumulate(rows[first:])
         # stream-ordered and asynchronous: the next segment is queued behind this copy while the host moves on (a blocking copy
         # here left the GPU idle for the gather + transfer + launch latency of every segment)
         kept[r:r + nr].copy_(rows if keep_all else rows[:, :, :, :1], non_blocking=True)
@@ -265,6 +281,9 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     quant_res = quant.result() if quant is not None else None
     if quant is not None:
         quant.free()
+    ppc_res = ppc.result() if ppc is not None else None
+    if ppc is not None:
+        ppc.free()
     summaries = []
     for q, (d_clean, c_clean, chain_file) in enumerate(files):
         chain0 = kept[:, q, :, 0].cpu().numpy()
@@ -289,6 +308,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             summ["quantiles"] = qn.json_record(quant_res, q, dr.file_labels + ["log-target"], args.quantile_bins)
             if doses is not None:
                 summ["curve_band"] = qn.curve_band_record(quant_res, q, doses[q])
+        if ppc_res is not None:
+            summ["ppc"] = pp.json_record(ppc_res[q], ppts, q)
         with open(chain_file[:-4] + "_summary.json", "w") as f:
             json.dump(summ, f, indent=1)
         summaries.append(summ)
@@ -305,6 +326,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         print(qn.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files],
                              [(quant_res["bin_width"][q, :n], quant_res["min"][q, :n], quant_res["max"][q, :n], quant_res["non_finite"][q, :n])
                               for q in range(len(files))]))
+    if ppc_res is not None:
+        print(pp.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], ppc_res))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, Q * C, total_iterations, time.time() - start - elapsed))
     return summaries

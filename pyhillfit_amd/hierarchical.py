@@ -542,8 +542,19 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             quant = qn.PosteriorQuantiles(Q, C, d + 1, saved_iterations - burn, args.quantile_probs, args.quantile_bins, device)
             if burn == 0:
                 quant.accumulate(s.row0.unsqueeze(0).contiguous())
+        ppc = None
+        if getattr(args, "ppc", False):                                # posterior predictive checks, accumulated like WAIC
+            from . import ppc as pp
+            from . import waic as wc
+            from .PyHillFit import experiments_and_labels
+            ppts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
+            pp.check_memory(pp.workspace_bytes(Q, ppts.stride, C, saved_iterations - burn), device)
+            ppc = pp.PosteriorPredictiveCheck(ppts, "hierarchical", Q, C, saved_iterations - burn, args.seed, [m[3] for m in members], 0,
+                                              device)
+            if burn == 0:
+                ppc.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, waic=waic, psis=psis, quant=quant, stream=torch.cuda.Stream(device=device)))
+                         diag=diag, waic=waic, psis=psis, quant=quant, ppc=ppc, stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
     fused = None
@@ -600,6 +611,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     run["psis"].accumulate(rows[first:])
                 if run["quant"] is not None and first < nr:
                     run["quant"].accumulate(rows[first:])
+                if run["ppc"] is not None and first < nr:
+                    run["ppc"].accumulate(rows[first:])
                 run["kept"][run["r"]:run["r"] + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # chain 0 of each pair
                 ev = torch.cuda.Event()
                 ev.record(run["stream"])
@@ -620,6 +633,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     waic_names, waic_parts = [], []
     loo_names, loo_parts = [], []
     quant_names, quant_parts = [], []
+    ppc_names, ppc_parts = [], []
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
         Q, C = len(members), args.num_chains
@@ -636,6 +650,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         quant_res = run["quant"].result() if run["quant"] is not None else None
         if quant_res is not None:
             run["quant"].free()
+        ppc_res = run["ppc"].result() if run["ppc"] is not None else None
+        if ppc_res is not None:
+            run["ppc"].free()
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
@@ -669,6 +686,11 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                 summ["quantiles"] = qn.json_record(quant_res, q, hierarchical_columns(ne), args.quantile_bins)
                 quant_names.append("{} + {}".format(d_clean, c_clean))
                 quant_parts.append((quant_res["bin_width"][q], quant_res["min"][q], quant_res["max"][q], quant_res["non_finite"][q]))
+            if ppc_res is not None:
+                from . import ppc as pp
+                summ["ppc"] = pp.json_record(ppc_res[q], run["ppc"].points, q)
+                ppc_names.append("{} + {}".format(d_clean, c_clean))
+                ppc_parts.append(ppc_res[q])
             with open(chain_file[:-4] + "_summary.json", "w") as f:
                 json.dump(summ, f, indent=1)
             summaries.append(summ)
@@ -685,6 +707,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     if getattr(args, "quantiles", False):
         from . import quantiles as qn
         print(qn.report_line(rank, quant_names, quant_parts))
+    if getattr(args, "ppc", False):
+        from . import ppc as pp
+        print(pp.report_line(rank, ppc_names, ppc_parts))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, total_chains, total_iterations, time.time() - start - elapsed))
     return summaries
