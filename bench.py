@@ -2,7 +2,7 @@
 """Benchmark of the hot path: MH samples/sec of the HIP sampler (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--iters-per-step I] [--model 1|2] [--moments]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
 
 A "step" is ONE pass of the sampler over the whole batch: every chain advanced by I Metropolis-Hastings iterations
 (thinned samples of all chains written to HBM).  The N=1 workload is the one BASELINE.json's metric is quoted on,
@@ -17,10 +17,11 @@ shards without a data-path collective (python/PyHillFit.py:978-1003 maps pairs o
                           (rank r owns chains [r C, (r+1) C) of every pair), value = all ranks' iterations / time;
   strong scaling:         the (pair, 64-chain block) units of ONE full-size workload are partitioned over the ranks by cost
                           (distributed.shard_blocks: 13 440 blocks -> 1 680 per GPU at 8), every chain keeping its Philox stream.
-With N > 1 BOTH are measured in the same run, one timed region each: `value` is the region --scaling names (weak by default),
-`strong_value` (or `weak_value`) the other.  With N = 1 the c3 run also times short regions of c2, c4, c5 and of the kernels the command
-lines and the thermodynamic-integration path launch — c5 with the on-device <log L> and moments (`c5_moments`), c3 with model 1
-(`c3_model1`) — (`other_workloads`).
+A plain run times the headline region alone: `value` is the region --scaling names (weak by default).  Everything else is measured
+with --full only: with N > 1 a second timed region of the other kind of scaling (`strong_value` or `weak_value`); with N = 1 the
+c3 run also times short regions of c2, c4, c5 and of the kernels the command lines and the thermodynamic-integration path
+launch — c5 with the on-device <log L> and moments (`c5_moments`), c3 with model 1 (`c3_model1`) — (`other_workloads`), and the
+reference loop on one CPU core (`cpu_baseline`).
 c4 (and a hierarchical strong-scaling share) launches the groups the gfx950 code object has kernels for — every pair with three or four
 experiments — as ONE persistent grid per step (phf_hierarchical_advance_fused), Ne = 5 / 6 beside it on streams of their own;
 PHF_BENCH_HIER_FUSED=0 gives every group a launch and a stream of its own (the arrangement before ABI 7), =3 fuses the Ne = 3 groups only — A/B
@@ -155,9 +156,10 @@ def parse_args(argv=None):
     ap.add_argument("--moments", action="store_true", help="also accumulate posterior moments and <log L> on the device (what the CLIs and the thermodynamic-integration path run)")
     ap.add_argument("--model", type=int, default=2, choices=[1, 2], help="single-level workloads: 2 = (pIC50, Hill, sigma) (BASELINE configs), 1 = (pIC50, sigma), Hill = 1")
     ap.add_argument("--queue-quanta", type=int, default=None, help="quanta per block of the work-queue launch (0: plain launch; default: the sampler's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="N = 1, c3: skip the short c2 / c4 / c5 regions after the headline")
-    ap.add_argument("--single-region", action="store_true", help="N > 1: only the region --scaling names (no second region of the other kind)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what it does not need: N > 1, the second region of the other "
+                    "kind of scaling; N = 1, the short regions of the other configurations (c3 defaults) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full, N = 1, c3: skip the short c2 / c4 / c5 regions after the headline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the headline region, write what its last step computed on rank 0 "
                     "(saved rows, their last row, per-chain acceptance) as DIR/<name>.npy, float64, 64 MB in all: arrays too large for "
                     "their share as a fixed seeded sample")
@@ -596,10 +598,10 @@ def main():
     del b
     release(torch)
 
-    # ---- N > 1: a second timed region in the same run with the OTHER kind of scaling.  The metric is "the full Crumb set at
+    # ---- --full, N > 1: a second timed region in the same run with the OTHER kind of scaling.  The metric is "the full Crumb set at
     # 1/2/4/8 GPUs": `value` keeps the per-GPU work fixed (weak), `strong_value` splits ONE full-size batch over the GPUs by
     # (pair, 64-chain block) units.  (N = 1: the two coincide.) ----
-    if world > 1 and not a.single_region:
+    if world > 1 and a.full:
         other = "strong" if a.scaling == "weak" else "weak"
         w2, C2, I2 = a.workload, C, I
         if other == "strong" and a.workload == "c3" and a.chains is None:
@@ -616,8 +618,8 @@ def main():
         del b2
         release(torch)
 
-    # ---- N = 1: the other BASELINE configurations, short regions of the same protocol, in the same JSON line ----
-    if world == 1 and a.workload == "c3" and a.chains is None and a.iters_per_step is None and not a.no_other_workloads \
+    # ---- --full, N = 1: the other BASELINE configurations, short regions of the same protocol, in the same JSON line ----
+    if a.full and world == 1 and a.workload == "c3" and a.chains is None and a.iters_per_step is None and not a.no_other_workloads \
             and a.model == 2 and not a.moments:
         others = {}
         for name in ("c2", "c4", "c5", "c5_moments", "c3_model1", "s3", "s3h"):
@@ -639,7 +641,7 @@ def main():
         out["other_workloads"] = others
 
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -206,15 +206,31 @@ def test_bench_line_keeps_the_contract(workload, tmp_path):
     assert chains == d["config"]["chains_per_gpu"]
 
 
+def test_bench_plain_default_run_times_the_headline_only():
+    """`bench.py` without --full (N = 1, defaults): the c3 headline and nothing else — no other configurations, no CPU baseline"""
+    import subprocess
+    import sys
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert "configs[2]" in d["config"]["workload"] and d["config"]["chains_per_gpu"] == 210 * 4096 and d["steps"] == 1 and d["value"] > 0
+    assert not {"other_workloads", "cpu_baseline", "strong_value", "strong_region"} & set(d), sorted(d)
+
+
 def test_bench_default_line_carries_the_other_configurations():
-    """the driver's command (N = 1, defaults): the headline keys are c3's, and `other_workloads` holds driver-timed short regions of
+    """`bench.py --full` (N = 1, defaults): the headline keys are c3's, and `other_workloads` holds driver-timed short regions of
     c2, c4, c5 and of the kernels the command lines and the thermodynamic-integration path launch — c5 with the on-device moments and
     <log L> (`c5_moments`), c3 with model 1 (`c3_model1`) — value, ms_per_step, kernel_ms and the two roofline fractions each"""
     import subprocess
     import sys
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -243,7 +259,7 @@ def test_bench_default_line_carries_the_other_configurations():
 
 
 def test_bench_two_ranks_default_strong_region_is_the_synthetic_s3_batch():
-    """the driver's N > 1 command (default workload): `value` is the weak-scaling C3 figure and `strong_value` the split of ONE batch
+    """`bench.py --gpus N --full` (default workload): `value` is the weak-scaling C3 figure and `strong_value` the split of ONE batch
     of SURVEY 8(d)'s synthetic set S3 (1 680 generated pairs x 4 096 chains in the real run; here 210 x 256 so that two ranks fit
     the one GPU of the rehearsal) by (pair, 64-chain block) units"""
     import subprocess
@@ -251,7 +267,7 @@ def test_bench_two_ranks_default_strong_region_is_the_synthetic_s3_batch():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "210", "--strong-chains", "256",
-           "--iters-per-step", "400", "--no-cpu-baseline"]
+           "--iters-per-step", "400", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, PHF_BENCH_BACKEND="gloo"))
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -262,7 +278,7 @@ def test_bench_two_ranks_default_strong_region_is_the_synthetic_s3_batch():
 
 
 def test_bench_two_ranks_split_the_hierarchical_synthetic_batch():
-    """`bench.py --gpus 2 --workload s3h` rehearsed on the one GPU (gloo): the weak value = two full batches of the hierarchical model on the
+    """`bench.py --gpus 2 --workload s3h --full` rehearsed on the one GPU (gloo): the weak value = two full batches of the hierarchical model on the
     generated set, `strong_value` = ONE batch split by (pair, 64-chain block) units — every rank's share is one launch of the gfx950
     assembly kernel (all generated pairs have three experiments of four points)"""
     import subprocess
@@ -270,7 +286,7 @@ def test_bench_two_ranks_split_the_hierarchical_synthetic_batch():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--workload", "s3h", "--pairs", "96", "--chains", "256", "--steps", "2", "--warmup", "1",
-           "--iters-per-step", "400", "--no-cpu-baseline"]
+           "--iters-per-step", "400", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, PHF_BENCH_BACKEND="gloo"))
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -282,14 +298,14 @@ def test_bench_two_ranks_split_the_hierarchical_synthetic_batch():
 
 
 def test_bench_two_ranks_report_weak_and_strong_scaling():
-    """`bench.py --gpus 2` rehearsed on the one GPU (gloo; RCCL refuses two ranks on a device): ONE JSON line with `value` (weak:
+    """`bench.py --gpus 2 --full` rehearsed on the one GPU (gloo; RCCL refuses two ranks on a device): ONE JSON line with `value` (weak:
     every rank its own full batch) AND `strong_value` (one batch split by (pair, 64-chain block) units, distributed.shard_blocks)"""
     import subprocess
     import sys
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--chains", "256",
-           "--iters-per-step", "400", "--no-cpu-baseline"]
+           "--iters-per-step", "400", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, PHF_BENCH_BACKEND="gloo"))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
