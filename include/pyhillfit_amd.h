@@ -575,6 +575,34 @@ int phf_stepping_stone_accumulate(const phf_points* pts, int model, const int32_
                                   int64_t total_rows, double* workspace, size_t workspace_bytes, void* stream);
 int phf_stepping_stone_reduce(int num_problems, int num_chains, int64_t total_rows, const double* workspace, size_t workspace_bytes,
                               double* out, void* stream);
+/* The standard error of a pair's log Z when its rungs are NOT independent (replica exchange: chain c of every rung is one replica set).
+ * Problems p*R .. p*R + R-1 are pair p's rungs in order (num_problems = num_pairs * rungs_per_pair); reduced is phf_stepping_stone_reduce's
+ * out.  Per chain v_c = sum_k<R-1 exp(log r_kc - log r_k); out[p] = sd_c(v_c) / sqrt(C) (divisor C - 1; NaN for one chain): the delta
+ * method over the C independent replica sets.  One wavefront per pair, chains merged in a fixed order. */
+int phf_stepping_stone_reduce_joint(int num_pairs, int rungs_per_pair, int num_chains, int64_t total_rows, const double* workspace,
+                                    size_t workspace_bytes, const double* reduced, double* out, void* stream);
+
+/* ---- replica exchange between the rungs of a tempered ladder ----------------------------------------------------------------
+ * (pyhillfit_amd/csrc/phf_replica_exchange.hip; DESIGN.md §3, "phf_replica_exchange.hip").  prob is the single-level sampler's batch
+ * with num_problems = P * rungs_per_pair, pair-major, rungs in temperature order; state its [S][Q*C] state.  Round `round` (>= 1)
+ * proposes the rung pairs (k, k+1), k = round (mod 2), chain c with chain c, and accepts iff log u < (t_k+1 - t_k)(l_k - l_k+1), l the
+ * state's untempered log-likelihood; on accept theta and l change slots and each slot's log-target is recomputed at its temperature
+ * as (t == 0 ? 0 : t l) + log-prior (the sampler's own arithmetic).  u = phf_uniform53 of the Philox block counter = (chain id,
+ * problem id of rung k, round, 0x40000000), key = seed.
+ *   labels   device int32 [Q*C], moves with the states: bits 0..27 the starting rung, bit 30 visited rung 0, bit 29 reached rung R-1
+ *            since (phf_replica_exchange_labels_init sets rung k's slots to k, rung 0's with bit 30)
+ *   stats    device, phf_replica_exchange_stats_bytes(...): int64 attempts and accepts per (pair, rung pair, 64-chain group) and round
+ *            trips 0 -> R-1 -> 0 per (pair, chain); phf_replica_exchange_stats_init zeroes it
+ *   trace    device double [P][R-1][C][3] or NULL: (u, log u, log alpha) of every proposed (pair, rung pair, chain) (tests)
+ * phf_replica_exchange_stats_read writes int64 attempts [P][R-1], accepts [P][R-1], round trips [P][C] to out (device).
+ * Deterministic: every slot and counter has one writer per round; no atomics. */
+size_t phf_replica_exchange_stats_bytes(int num_pairs, int rungs_per_pair, int num_chains);
+int phf_replica_exchange_stats_init(int num_pairs, int rungs_per_pair, int num_chains, int64_t* stats, size_t stats_bytes, void* stream);
+int phf_replica_exchange_stats_read(int num_pairs, int rungs_per_pair, int num_chains, const int64_t* stats, size_t stats_bytes,
+                                    int64_t* out, void* stream);
+int phf_replica_exchange_labels_init(int num_pairs, int rungs_per_pair, int num_chains, int32_t* labels, void* stream);
+int phf_replica_exchange_round(const phf_problems* prob, int model, int rungs_per_pair, int64_t round, uint64_t seed, double* state,
+                               int32_t* labels, int64_t* stats, size_t stats_bytes, double* trace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@ chain 0 is written, burn-in removed, headerless, to the reference's temperature_
 python/compute_bayes_factors.py expects it.  Start point ones(d), identity covariance, mean reset at 1000*d
 (:63,80,114-115).  `--diagnostics` adds split-R-hat / ESS / MCSE of every (pair, rung) over all its chains.  `--rungs N` changes n (BASELINE config 5 uses 32 rungs = --rungs 31).  `-nc N` — the reference's pool size —
 starts min(N, visible GPUs) ranks, one per GPU, which share the (pair, rung) units; or launch under torchrun.
-`--stepping-stone` adds the stepping-stone estimate of log Z with its standard error (pyhillfit_amd/stepping_stone.py)."""
+`--stepping-stone` adds the stepping-stone estimate of log Z with its standard error (pyhillfit_amd/stepping_stone.py).
+`--swap-every K` adds replica-exchange swaps between adjacent rungs after every K iterations (pyhillfit_amd/replica_exchange.py)."""
 import argparse
 import json
 import sys
@@ -57,13 +58,21 @@ def build_parser():
     new.add_argument("--stepping-stone", action='store_true', default=False, help="stepping-stone estimate of log Z (Xie et al. 2011) "
                      "with standard errors and per-rung importance-weight ESS, accumulated on the GPU from the same rows; written to "
                      "thermodynamic_integration.json (\"stepping_stone\") and the rung records")
+    new.add_argument("--swap-every", type=int, default=0, help="K > 0: replica-exchange swaps between adjacent rungs of each pair after "
+                     "every K iterations (even-odd scheme; chain c with chain c), written to thermodynamic_integration.json "
+                     "(\"replica_exchange\"); the standard errors then treat each chain index as one replica set.  0 (default): "
+                     "independent rungs, as the reference")
     return parser
 
 
-def partition_units(points_per_pair, num_rungs, world):
+def partition_units(points_per_pair, num_rungs, world, whole_pairs=False):
     """The work units of a tempered run are (pair, rung): the reference maps the RUNGS of one pair over its process pool
     (python/PyHillTemp.py:151-161), so `-d D -c C` on 8 GPUs must spread the 41 rungs, and --all-pairs spreads pairs x rungs.
-    Returns, per rank, a sorted array of unit numbers u = pair * num_rungs + rung (cost of a unit ~ the pair's points)."""
+    Returns, per rank, a sorted array of unit numbers u = pair * num_rungs + rung (cost of a unit ~ the pair's points).
+    whole_pairs (replica exchange: swaps never cross ranks): all rungs of a pair go to one rank; surplus ranks get no units."""
+    if whole_pairs:
+        pairs = phfdist.shard_problems(np.asarray(points_per_pair, dtype=np.float64) * num_rungs, world)
+        return [(p[:, None] * num_rungs + np.arange(num_rungs)[None, :]).reshape(-1).astype(np.int64) for p in pairs]
     costs = np.repeat(np.asarray(points_per_pair, dtype=np.float64), num_rungs)
     return phfdist.shard_problems(costs, world)
 
@@ -137,6 +146,29 @@ def attach_stepping_stone(rungs, tis, unit_rows, first, temperatures, chains):
     return out
 
 
+def attach_replica_exchange(rungs, tis, unit_rows, first, temperatures, chains, every, ss_recs=None):
+    """the gathered per-unit replica-exchange columns (first.. of unit_rows, replica_exchange.UNIT_COLUMNS) onto the pair records
+    ("replica_exchange", "expectation_se_replica_sets") and the rung records ("swap_accept_rate": with the next rung); with
+    --stepping-stone the pair's se becomes the one over replica sets.  Returns the pair objects."""
+    from . import replica_exchange as rx
+    R = len(temperatures)
+    unit_rows = unit_rows[np.lexsort((unit_rows[:, 1], unit_rows[:, 0]))]
+    v = unit_rows[:, first:first + len(rx.UNIT_COLUMNS)]
+    out = []
+    for ip, ti in enumerate(tis):
+        rec = rx.json_record(v[ip * R:(ip + 1) * R], temperatures, chains, every)
+        for ir in range(R):
+            rungs[ip * R + ir]["swap_accept_rate"] = rec["accept_rate"][ir] if ir < R - 1 else None
+        ti["replica_exchange"] = rec
+        ti["expectation_se_replica_sets"] = rx._num(v[ip * R, 5])
+        if ss_recs is not None:
+            ss_recs[ip]["se_independent_rungs"] = ss_recs[ip]["se"]
+            ss_recs[ip]["se"] = rx._num(v[ip * R, 4])
+            ss_recs[ip]["se_method"] = "replica_sets"
+        out.append(rec)
+    return out
+
+
 def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     """pairs: [(drug, channel)] of the WHOLE run; one problem per (pair, rung), this rank's share of them sampled here.
     Every rank writes the chain files of its own units; rank 0 gathers the per-unit expectations, writes one
@@ -150,7 +182,10 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     for drug, channel in pairs:
         num_expts, _, experiments = dr.load_crumb_data(drug, channel)
         loaded.append((drug, channel) + tuple(dr.concatenate_experiments(num_expts, experiments)))   # PyHillTemp.py:130-136
-    mine = partition_units([len(c) for _, _, c, _ in loaded], R, world)[rank]
+    swap = args.swap_every
+    if swap < 0:
+        raise SystemExit("--swap-every must be 0 (off) or a positive number of iterations")
+    mine = partition_units([len(c) for _, _, c, _ in loaded], R, world, whole_pairs=swap > 0)[rank]
     my_pairs = sorted(set(int(u) // R for u in mine))
     local_of = {ip: k for k, ip in enumerate(my_pairs)}
     C = args.num_chains
@@ -167,6 +202,10 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     if args.stepping_stone:       # per unit: stepping_stone.OUT; they ride on the same gather
         from . import stepping_stone as ss
         unit_rows = np.concatenate([unit_rows, np.zeros((len(mine), len(ss.OUT)))], axis=1)
+    rx_first = unit_rows.shape[1]
+    if swap > 0:                  # per unit: replica_exchange.UNIT_COLUMNS; they ride on the same gather
+        from . import replica_exchange as rxm
+        unit_rows = np.concatenate([unit_rows, np.zeros((len(mine), len(rxm.UNIT_COLUMNS)))], axis=1)
     # the rows the fused <log L(t=1)> counts: saved rows with t > moments_after, i.e. row index >= max(burn, 1)
     first_kept = max(burn, 1)
     mcmc_time = 0.0
@@ -200,12 +239,13 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
             delta = ss.deltas(temperatures)
             ss.check_memory(ss.workspace_bytes(Q, C, num_saved - first_kept), device)
             sst = ss.SteppingStone(s.points, model, pair_index, [float(delta[int(u) % R]) for u in mine], C, num_saved - first_kept, device)
+        rx = rxm.ReplicaExchange(s, R) if swap > 0 else None      # the units are whole pairs, pair-major, rungs in order
         done, r = 0, 1
         start = time.time()
         while done < total_iterations:
             k = min(seg, total_iterations - done)
             nr = k // thinning
-            rows = s.advance(k, out=buf[:nr])
+            rows = s.advance(k, out=buf[:nr]) if rx is None else rx.advance(k, every=swap, out=buf[:nr])
             first = max(0, burn - r)                                    # saved rows before `burn` are the burn-in
             if diag is not None and first < nr:
                 diag.accumulate(rows[first:])
@@ -226,7 +266,12 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
             print(dg.report_line(rank, ["{} + {} at t = {:g}".format(loaded[int(u) // R][0], loaded[int(u) // R][1], temperatures[int(u) % R])
                                         for u in mine], res["rhat"], res["ess"]))
         if sst is not None:
-            unit_rows[:, ss_first:] = sst.reduced()
+            unit_rows[:, ss_first:ss_first + len(ss.OUT)] = sst.reduced()
+        if rx is not None:
+            se_joint = rxm.joint_se(sst, len(my_pairs), R) if sst is not None else None
+            unit_rows[:, rx_first:] = rxm.unit_columns(rx.statistics(), rx.rounds, len(my_pairs), R, se_joint,
+                                                       rxm.replica_set_ti_se(ll1, temperatures, len(my_pairs)))
+        if sst is not None:
             sst.free()
         for q, u in enumerate(mine):
             ip, ir = int(u) // R, int(u) % R
@@ -247,9 +292,16 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     out, tis = assemble_thermodynamic_integration(gathered[:, :width], [(l[0], l[1]) for l in loaded], temperatures, model, facts)
     if args.diagnostics:
         attach_diagnostics(out, tis, gathered[:, :ss_first], width, d + 1, R, C, num_saved - burn, args.diagnostic_lags)
+    ss_recs = None
+    if args.stepping_stone:
+        ss_recs = attach_stepping_stone(out, tis, gathered, ss_first, temperatures, C)
+    if swap > 0:
+        from . import replica_exchange as rxm
+        for (drug, channel, _, _), rec in zip(loaded, attach_replica_exchange(out, tis, gathered, rx_first, temperatures, C, swap, ss_recs)):
+            print(rxm.report_line(drug, channel, model, rec, temperatures))
     if args.stepping_stone:
         from . import stepping_stone as ss
-        for (drug, channel, _, _), rec in zip(loaded, attach_stepping_stone(out, tis, gathered, ss_first, temperatures, C)):
+        for (drug, channel, _, _), rec in zip(loaded, ss_recs):
             print(ss.report_line(drug, channel, model, rec))
     for (drug, channel, _, _), ti in zip(loaded, tis):
         with open(thermodynamic_integration_file(model, drug, channel), "w") as f:
@@ -274,6 +326,8 @@ def main(argv=None):
         parser.print_help()
         sys.exit(1)
     args = parser.parse_args(argv)
+    if args.swap_every < 0:
+        parser.error("--swap-every must be 0 (off) or a positive number of iterations")
     n = phfdist.ranks_for_cores(args.num_cores)                         # -nc N: the reference's pool over the rungs (:155-159) -> N ranks
     if n:
         sys.exit(phfdist.spawn_ranks("pyhillfit_amd.PyHillTemp", sys.argv[1:] if argv is None else argv, n))

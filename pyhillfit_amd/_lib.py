@@ -19,7 +19,9 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_psis_workspace_bytes", "phf_psis_init", "phf_psis_accumulate", "phf_psis_reduce", "phf_quantiles_workspace_bytes",
            "phf_quantiles_init", "phf_quantiles_accumulate", "phf_quantiles_accumulate_curves", "phf_quantiles_reduce",
            "phf_ppc_workspace_bytes", "phf_ppc_init", "phf_ppc_accumulate", "phf_ppc_reduce", "phf_ppc_replicate", "phf_stepping_stone_workspace_bytes",
-           "phf_stepping_stone_init", "phf_stepping_stone_accumulate", "phf_stepping_stone_reduce"]
+           "phf_stepping_stone_init", "phf_stepping_stone_accumulate", "phf_stepping_stone_reduce", "phf_stepping_stone_reduce_joint",
+           "phf_replica_exchange_stats_bytes", "phf_replica_exchange_stats_init", "phf_replica_exchange_stats_read",
+           "phf_replica_exchange_labels_init", "phf_replica_exchange_round"]
 
 
 class PhfError(RuntimeError):
@@ -128,6 +130,13 @@ def load():
     lib.phf_stepping_stone_init.argtypes = [i32, i32, i64, vp, C.c_size_t, vp]
     lib.phf_stepping_stone_accumulate.argtypes = [C.POINTER(Points), i32, vp, vp, vp, i64, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
     lib.phf_stepping_stone_reduce.argtypes = [i32, i32, i64, vp, C.c_size_t, vp, vp]
+    lib.phf_stepping_stone_reduce_joint.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp, vp, vp]
+    lib.phf_replica_exchange_stats_bytes.argtypes = [i32, i32, i32]
+    lib.phf_replica_exchange_stats_bytes.restype = C.c_size_t
+    lib.phf_replica_exchange_stats_init.argtypes = [i32, i32, i32, vp, C.c_size_t, vp]
+    lib.phf_replica_exchange_stats_read.argtypes = [i32, i32, i32, vp, C.c_size_t, vp, vp]
+    lib.phf_replica_exchange_labels_init.argtypes = [i32, i32, i32, vp, vp]
+    lib.phf_replica_exchange_round.argtypes = [C.POINTER(Problems), i32, i32, i64, C.c_uint64, vp, vp, vp, C.c_size_t, vp, vp]
     _lib = lib
     return lib
 

@@ -57,7 +57,7 @@ def log_z_stepping_stone_from_chain_files(model, drug, channel, temperatures, co
 
 def stepping_stone_main(args, top_drug, top_channel, concs, responses, temps):
     """--estimator stepping-stone: log B12 = log Z_1 - log Z_2 with se = sqrt(se_1^2 + se_2^2)"""
-    log_z, se, sources = {}, {}, {}
+    log_z, se, sources, methods = {}, {}, {}, {}
     for m in (1, 2):
         dr.define_model(m)
         ti_file = thermodynamic_integration_file(m, top_drug, top_channel)
@@ -76,11 +76,13 @@ def stepping_stone_main(args, top_drug, top_channel, concs, responses, temps):
         rec = ti["stepping_stone"]
         log_z[m] = float(rec["log_z"]) if rec["log_z"] is not None else float("nan")
         se[m], sources[m] = rec["se"], "stepping stone"
+        methods[m] = rec.get("se_method", "independent_rungs")     # "replica_sets": PyHillTemp --swap-every
     log_b12 = log_z[1] - log_z[2]
     log_b12_se = None if se[1] is None or se[2] is None else float(np.sqrt(se[1] ** 2 + se[2] ** 2))
     print(log_z)
+    over = " over replica sets" if methods and all(v == "replica_sets" for v in methods.values()) else ""
     print("log B12 = {:.6g} +- {}".format(log_b12, "n/a (one chain)" if log_b12_se is None else
-                                          "{:.3g} (between-chain Monte Carlo error only, blind to a bias the chains share)".format(log_b12_se)))
+                                          "{:.3g} (between-chain Monte Carlo error{} only, blind to a bias the chains share)".format(log_b12_se, over)))
     drug, channel, _, _ = dr.nonhierarchical_chain_file_and_figs_dir(1, top_drug, top_channel, 1)
     if not os.path.exists(args.bf_dir):
         os.makedirs(args.bf_dir)
@@ -88,7 +90,7 @@ def stepping_stone_main(args, top_drug, top_channel, concs, responses, temps):
     B12 = np.exp(log_b12)
     np.savetxt(bf_file, [B12])
     return {"B12": float(B12), "expectations": log_z, "sources": sources, "file": bf_file, "log_B12": float(log_b12),
-            "log_B12_se": log_b12_se, "estimator": "stepping-stone"}
+            "log_B12_se": log_b12_se, "estimator": "stepping-stone", "se_methods": methods}
 
 
 def main(argv=None):

@@ -237,6 +237,22 @@ PHF_HD void phf_sl_log_target_shared(int model, const double* lc, const double* 
 #undef PHF_SHARE_PUT_
 #undef PHF_CDEN_
 
+/* The log-prior part of phf_sl_log_target alone, in exactly its fp64 operations: what a replica-exchange swap (phf_replica_exchange.hip)
+ * adds to t l when a state moves to another rung, so that the moved state's log-target is the double the sampler itself would hold. */
+PHF_HD double phf_sl_log_prior(int model, const double* th, phf_ktab k_log) {
+  const double pic50 = th[0];
+  const double hill = (model == 1) ? 1.0 : th[1];
+  const double sigma = (model == 1) ? th[1] : th[2];
+  const double sl = sigma - PHF_SIGMA_LOC;
+  const double log_sl = phf_log_pos_k(sl, k_log);
+  const int outside = (pic50 < PHF_PIC50_LOWER)
+                      | (sigma <= PHF_SIGMA_LOC)
+                      | ((model == 2) & ((hill < 0.0) | (hill > PHF_HILL_UPPER)));
+  const double g = phf_fma(PHF_SIGMA_SHAPE_M1, log_sl, -sl * PHF_SIGMA_INV_SCALE);
+  const double lp = -PHF_PIC50_RATE * pic50 + g;
+  return outside ? -PHF_INF : lp;
+}
+
 /* The random numbers of MH iteration t of one chain — ONE Philox4x32-10 block (128 bits) per iteration:
  *   d == 2: z0, z1 from words 0, 1 (phf_normal_u32: piecewise inverse CDF of a 31-bit uniform + a sign bit, |z| <= 6.34),
  *           accept uniform from words 2, 3 (53 bits: numpy's random_sample construction);

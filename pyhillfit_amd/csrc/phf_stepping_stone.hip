@@ -186,6 +186,29 @@ __global__ __launch_bounds__(kThreads) void ss_reduce_kernel(const SsArgs a) {
   }
 }
 
+// out[p] = sd_c(v_c) / sqrt(C), v_c = sum_k<R-1 r_kc / r_k over pair p's rungs (replica sets); one wavefront per pair
+__global__ __launch_bounds__(kThreads) void ss_reduce_joint_kernel(const SsArgs a, int num_pairs, int rungs, const double* reduced) {
+  const int p = (int)(blockIdx.x * kWaves + threadIdx.x / 64);
+  if (p >= num_pairs) return;
+  const int lane = threadIdx.x & 63;
+  const size_t C = (size_t)a.C;
+  Part part = {0.0, 0.0, 0.0};
+  for (int c = lane; c < a.C; c += 64) {
+    double v = 0.0;
+    for (int k = 0; k < rungs - 1; ++k) {
+      const int q = p * rungs + k;
+      const double* st = a.ws + (size_t)q * kFields * C;
+      v += exp(chain_log_r(st[c], st[C + c], st[4 * C + c]) - reduced[(size_t)q * kOut]);
+    }
+    part = part_merge(part, Part{1.0, v, 0.0});
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const Part op = {__shfl_xor(part.n, o, 64), __shfl_xor(part.mean, o, 64), __shfl_xor(part.m2, o, 64)};
+    part = (lane & o) ? part_merge(op, part) : part_merge(part, op);
+  }
+  if (lane == 0) a.out[p] = a.C > 1 ? sqrt(part.m2 / (part.n - 1.0)) / sqrt((double)a.C) : PHF_NAN;
+}
+
 unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 int check_shape(const char* who, int num_problems, int num_chains, int64_t total_rows) {
@@ -271,4 +294,21 @@ extern "C" int phf_stepping_stone_reduce(int num_problems, int num_chains, int64
   a.Q = num_problems; a.C = num_chains; a.total_rows = total_rows; a.ws = const_cast<double*>(workspace); a.out = out;
   hipLaunchKernelGGL(ss_reduce_kernel, dim3(blocks_for(num_problems, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   return phf_check_launch("ss_reduce_kernel");
+}
+
+extern "C" int phf_stepping_stone_reduce_joint(int num_pairs, int rungs_per_pair, int num_chains, int64_t total_rows, const double* workspace,
+                                               size_t workspace_bytes, const double* reduced, double* out, void* stream) {
+  if (num_pairs < 1 || rungs_per_pair < 1 || (double)num_pairs * rungs_per_pair > 2147483647.0)
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce_joint: num_pairs and rungs_per_pair must be positive");
+  const int Q = num_pairs * rungs_per_pair;
+  int rc = check_shape("phf_stepping_stone_reduce_joint", Q, num_chains, total_rows);
+  if (rc != PHF_OK) return rc;
+  if (!workspace || !reduced || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce_joint: null pointer");
+  if (workspace_bytes < workspace_bytes_of(Q, num_chains))
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce_joint: workspace smaller than phf_stepping_stone_workspace_bytes()");
+  SsArgs a = {};
+  a.Q = Q; a.C = num_chains; a.total_rows = total_rows; a.ws = const_cast<double*>(workspace); a.out = out;
+  hipLaunchKernelGGL(ss_reduce_joint_kernel, dim3(blocks_for(num_pairs, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a,
+                     num_pairs, rungs_per_pair, reduced);
+  return phf_check_launch("ss_reduce_joint_kernel");
 }
