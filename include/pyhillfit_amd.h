@@ -325,7 +325,9 @@ int phf_hierarchical_log_target(const phf_hier_points* pts, const phf_hier_prior
  * 18 phf_log_ndtr_tab(x): log Phi(x) from the censored likelihood's table (valid for -185 000 < x <= 0; any x is safe to pass);
  * 19 phf_erfc_tab(y): erfc(y), y >= 0, to 3.6e-17 absolute from the hierarchical target's table, 0 from y = 6 on (any y is safe to pass);
  * 20 / 21 phf_sqrt_rcp_pos(x): the reciprocal 1 / sqrt(x) (of the ROUNDED root) / the root itself — a Cholesky pivot and its reciprocal
- * from one hardware estimate (ABI 5; python/PyHillFit.py:831 draws through numpy's factorisation of the same covariance). */
+ * from one hardware estimate (ABI 5; python/PyHillFit.py:831 draws through numpy's factorisation of the same covariance);
+ * 22: n even, in = n / 2 pairs (x, w) (w an integer value in [0, 2^32)): out[2 i] = phf_mh_accept_u32(x, w) (the single-level sampler's
+ * accept test for d = 3), out[2 i + 1] = phf_log_pos_k((w + 1/2) / 2^32) < x, each 1.0 or 0.0. */
 int phf_debug_math(int fn, int64_t n, const double* in, double* out, void* stream);
 
 /* The same for the hand-allocated gfx950 code object (ABI 6; tools/gen_hier_isa.py, tools/isa/phf_isa_math.py): every elementary

@@ -275,4 +275,41 @@ PHF_HD double phf_mh_draws(int d, uint32_t chain_id, uint32_t problem_id, uint32
   return phf_log_pos_k(phf_unit_open32(b.w[3]), k_log);  /* u = (w + 1/2) / 2^32 is never 0 */
 }
 
+/* d == 3 only: the same block and the same three normals as phf_mh_draws, and the accept WORD w (u = (w + 1/2) / 2^32) in place of
+ * log u — for phf_mh_accept_u32, which decides log u < x without the logarithm for nearly every w. */
+PHF_HD uint32_t phf_mh_draws_w3(uint32_t chain_id, uint32_t problem_id, uint32_t t, uint32_t seed_lo, uint32_t seed_hi, double* z) {
+  const phf_u32x4 b = phf_philox_mh(chain_id, problem_id, t, 0u, seed_lo, seed_hi);
+  z[0] = phf_normal_u32(b.w[0]);
+  z[1] = phf_normal_u32(b.w[1]);
+  z[2] = phf_normal_u32(b.w[2]);
+  return b.w[3];
+}
+
+/* The Metropolis test  phf_log_pos_k(phf_unit_open32(w)) < x  of the d == 3 draws: the same answer for every w and every x (NaN, +-0,
+ * +-inf included), with the logarithm evaluated only when some lane of the wavefront has its word next to the threshold.
+ * u_w < e^x  <=>  w + 1/2 < T = 2^32 e^x, and the device estimates T in fp32:
+ *   t = v_exp_f32(fma((float) x, log2 e, 32)) = T (1 + tau),  |tau| < 4e-6 for x <= 0 (the fp32 roundings of x, of log2 e and of
+ *   the argument, and 2^-20 allowed for v_exp_f32: DESIGN.md section 3), so |t - T| < 2^15 words.
+ * A word with |w - t| > 2^18 (one in 2^13 per lane and iteration lands inside) is decided by the sign of w - t: the band covers the
+ * estimate's error eight times over, plus the fp32 rounding of w and of w - t (<= 256 words), the 1/2 of u_w, and the logarithm's
+ * own error E = 3.5e-15 (max over all 2^32 words of |phf_log_pos_k(u_w) - ln u_w|: tests/test_accept_u32_host.py), which moves the
+ * exact threshold by E T < 1e-4 words.  Inside the band the logarithm decides.  x > 0: t >= 2^32 (1 - tau), every w outside the
+ * band accepts; NaN: every comparison is false, reject; x = -inf: t = 0, w > 2^18 rejects and the rest take the logarithm, which
+ * rejects.  The host (the twin does not call this) evaluates the comparison itself. */
+#define PHF_ACCEPT_U32_BAND 0x1p18f
+PHF_HD int phf_mh_accept_u32(double x, uint32_t w, phf_ktab k_log) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float t = __builtin_amdgcn_exp2f(__builtin_fmaf((float)x, 0x1.715476p+0f, 32.0f));
+  const float dw = (float)w - t;
+  bool acc = dw < 0.0f;
+  if (PHF_ANY_LANE(__builtin_fabsf(dw) <= PHF_ACCEPT_U32_BAND)) {   /* wave-uniform: the logarithm runs only when a lane needs it */
+    const bool exact = phf_log_pos_k(phf_unit_open32(w), k_log) < x;
+    acc = (__builtin_fabsf(dw) <= PHF_ACCEPT_U32_BAND) ? exact : acc;
+  }
+  return acc;
+#else
+  return phf_log_pos_k(phf_unit_open32(w), k_log) < x;
+#endif
+}
+
 #endif /* PHF_MODEL_H */

@@ -170,8 +170,13 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
   // function of (chain, t+1) only — are drawn next to the factorisation of iteration t, so that the two long dependency
   // chains of an iteration (Philox -> log -> sqrt, and sqrt -> divide -> sqrt -> divide -> sqrt) overlap each other and
   // the likelihood instead of being exposed one after the other on a wavefront that has its SIMD to itself.
+  // d = 3 carries the accept word itself, not log u: phf_mh_accept_u32 needs the logarithm only near the threshold (at most one iteration
+  // of a wavefront in 128); d = 2 (a 53-bit uniform) keeps the logarithm.
   double z[3];
-  double log_u = phf_mh_draws(D, cid, pid, (uint32_t)(t_begin + 1), seed_lo, seed_hi, k_log, z);
+  double log_u = 0.0;
+  uint32_t w_u = 0u;
+  if constexpr (D == 3) w_u = phf_mh_draws_w3(cid, pid, (uint32_t)(t_begin + 1), seed_lo, seed_hi, z);
+  else log_u = phf_mh_draws(D, cid, pid, (uint32_t)(t_begin + 1), seed_lo, seed_hi, k_log, z);
   const bool reset_mean = a.cfg.reset_mean_at_adapt_start != 0;
   for (int64_t t = t_begin + 1; t <= t_end; ++t) {
     // ---- proposal: theta* = theta + e^(loga/2) L z  (PyHillFit.py:831) ----
@@ -188,7 +193,7 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
     phf_sl_log_target_shared(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature, star, k_exp, k_log,
                              SHARE, den_off, s_den + threadIdx.x, kBlock, &lik_star, &prior_star, &ll1_star);
     const double lt_star = lik_star + prior_star;
-    const bool acc = log_u < lt_star - lt;
+    const bool acc = (D == 3) ? (bool)phf_mh_accept_u32(lt_star - lt, w_u, k_log) : log_u < lt_star - lt;
     if (acc) {
 #pragma unroll
       for (int i = 0; i < D; ++i) th[i] = star[i];
@@ -218,12 +223,16 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
     }
     // ---- draws of the next iteration, factor and scale of the next proposal ----
     double z_next[3];
-    const double log_u_next = phf_mh_draws(D, cid, pid, (uint32_t)(t + 1), seed_lo, seed_hi, k_log, z_next);
+    double log_u_next = 0.0;
+    uint32_t w_u_next = 0u;
+    if constexpr (D == 3) w_u_next = phf_mh_draws_w3(cid, pid, (uint32_t)(t + 1), seed_lo, seed_hi, z_next);
+    else log_u_next = phf_mh_draws(D, cid, pid, (uint32_t)(t + 1), seed_lo, seed_hi, k_log, z_next);
     chol_packed<D>(cov, L);
     sc = phf_exp_fast_k(0.5 * loga, k_exp);
 #pragma unroll
     for (int i = 0; i < 3; ++i) z[i] = z_next[i];
     log_u = log_u_next;
+    w_u = w_u_next;
     // ---- thinning + sample store (PyHillFit.py:847-848) ----
     if (--until_save == 0) {
       until_save = thin;
@@ -484,6 +493,15 @@ __global__ void debug_math_kernel(int fn, int64_t n, const double* in, double* o
   PHF_ERFC_TABLE_TO_LDS();
   PHF_NORMAL_TABLE_TO_LDS();
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (fn == 22) {                                      // pairs (x, w): the sampler's accept test and the logarithm's own comparison
+    if (2 * i + 1 >= n) return;
+    PHF_KFETCH_V(k_log, phf_k_log, PHF_K_LOG_N);
+    const double x = in[2 * i];
+    const uint32_t w = (uint32_t)in[2 * i + 1];
+    out[2 * i] = phf_mh_accept_u32(x, w, k_log) ? 1.0 : 0.0;
+    out[2 * i + 1] = (phf_log_pos_k(phf_unit_open32(w), k_log) < x) ? 1.0 : 0.0;
+    return;
+  }
   if (i >= n) return;
   const double x = in[i];
   double r, s, c;
@@ -688,7 +706,7 @@ int phf_single_level_log_target(const phf_points* pts, int model, int64_t m, con
 }
 
 int phf_debug_math(int fn, int64_t n, const double* in, double* out, void* stream) {
-  if (fn < 0 || fn > 21 || n < 0 || !in || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "bad arguments to phf_debug_math");
+  if (fn < 0 || fn > 22 || n < 0 || (fn == 22 && n % 2) || !in || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "bad arguments to phf_debug_math");
   if (n == 0) return PHF_OK;
   hipLaunchKernelGGL(debug_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fn, n, in, out);
   return phf_check_launch("phf_debug_math");
