@@ -40,12 +40,26 @@ seeds 301, 302, 311..318 — under the bar exactly as it stands in the tree at t
 its sd within 20 % + 4 standard errors of the reference's pooled sd (which 48 seeds make ~2.2 x narrower than ten did), acceptance within 0.02.
 Whatever fails is a finding about the sampler to chase, not a pair to name, and no further seeds are added.
 
+G11 (--few-experiments; THIS RULE WAS WRITTEN BEFORE ANY OF ITS RUNS EXISTED): the sampler promises 1 <= Ne <= 64 and the command line's
+-Ne keeps the first Ne experiments of a pair (PyHillFit.py:228-231), but G10..G10e pin Ne = 3..6 only.  G11 runs the same lifted loop on
+the first four of PAIRS (Amiodarone-hERG, Amiodarone-Kv4.3, Dofetilide-hERG, Amitriptyline-Kv4.3), each cut to its first 1 and its first 2
+experiments: 8 cases in that order (pair-major, Ne = 1 then 2).  Seeds 501..508, the same for every case, no case gets more; 500 000
+iterations, thinning 5, the first quarter of the saved rows dropped; the start point is bestfit.hierarchical_first_iteration of the CUT pair,
+stored in the fixture.  Written to g11_hier_posteriors_few_experiments.json in G10's record layout (quantiles kept).  The GPU test holds a
+fresh run (512 chains per case, a seed not used before) to these seeds under the bar as it stands: mean within 1 % + 4 standard errors, sd
+within 20 % + 4 standard errors of the reference's pooled sd, acceptance within 0.02, no case and no column exempt.  Before the first GPU
+run the CPU twin (32 chains per case) is put through the same comparison (tests/golden/precheck_few_experiments.py ->
+profiles/few_experiments/cpu_precheck.txt).  The one follow-up the rule allowed — 8 further seeds 511..518, only for cases where the reference's
+seeds 501..504 fail that bar against 505..508 — was not needed: the twin passed every column of all 8 cases (worst mean ratio 0.26 of the bar, sd
+ratios 0.98..1.02) and so do the reference's two halves against each other.  No case may be reseeded now.
+
 TEST INFRASTRUCTURE, generator side only (needs /root/reference; 18 runs of 3-6 minutes spread over worker processes).
     python tests/golden/make_golden_posteriors_hier.py [--iterations 500000] [--seeds 3] [--workers 7]
     python tests/golden/make_golden_posteriors_hier.py --per-drug [--workers 5]          (60 runs of 4-8 minutes)
     python tests/golden/make_golden_posteriors_hier.py --all-remaining [--workers 7]     (348 runs: ~4 hours on 7 cores)
     python tests/golden/make_golden_posteriors_hier.py --follow-up [--workers 7]         (64 runs: ~50 minutes)
     python tests/golden/make_golden_posteriors_hier.py --replication [--workers 6]       (144 runs: ~95 minutes)
+    python tests/golden/make_golden_posteriors_hier.py --few-experiments [--workers 7]   (64 runs of 2-4 minutes: ~30 minutes)
 """
 import argparse
 import contextlib
@@ -80,6 +94,10 @@ FOLLOW_UP_SEEDS = tuple(range(311, 319))
 REPLICATION = [("Azithromycin", "Kir2.1"), ("Ranolazine", "Cav1.2"), ("Dofetilide", "Cav1.2")]
 REPLICATION_SEEDS = tuple(range(401, 449))
 
+# G11: the pre-registered few-experiment cases (see the docstring): the first four of PAIRS cut to their first 1 and first 2 experiments
+FEW_EXPERIMENTS = [(d, c, ne) for d, c in PAIRS[:4] for ne in (1, 2)]
+FEW_EXPERIMENTS_SEEDS = tuple(range(501, 509))
+
 NB = 25                                   # batches for the batch-means standard error
 
 
@@ -95,6 +113,9 @@ def _run(job):
     dr = R.load_doseresponse()
     dr.setup(os.path.join(G.REF_DATA, "crumb_data.csv"))
     pair = G.concat_pair(dr, d, c)
+    ne = (len(first_iteration) - 5) // 2                  # all of the pair's experiments, or (G11) its first ne: PyHillFit.py:228-231
+    assert 1 <= ne <= len(pair["experiments"])
+    pair["experiments"] = [x for x in pair["experiments"][:ne]]
     shapes, scales, locs, _ = G.elkins_prior_params()
     glb = {"np": np, "sys": sys, "st": st, "pic50_prior": [-2.], "dr": dr}
     R.lift_functions("PyHillFit.py", ["log_data_likelihood", "log_hill_i_log_logistic_likelihood", "log_pic50_i_logistic_likelihood",
@@ -130,6 +151,7 @@ def main():
     ap.add_argument("--all-remaining", action="store_true", help="G10c: every pair in neither G10 nor G10b, seeds 301, 302 (resumable)")
     ap.add_argument("--follow-up", action="store_true", help="G10d: the FOLLOW_UP pairs, seeds 311..318 (resumable)")
     ap.add_argument("--replication", action="store_true", help="G10e: the REPLICATION pairs, 48 fresh seeds 401..448 (resumable)")
+    ap.add_argument("--few-experiments", action="store_true", help="G11: the first four PAIRS cut to 1 and 2 experiments, seeds 501..508 (resumable)")
     a = ap.parse_args()
     import _ref_loader as R
     import make_golden as G
@@ -145,6 +167,8 @@ def main():
                              keep_quantiles=True)
     if a.replication:
         return all_remaining(a, dr, locs, pairs=list(REPLICATION), seeds=REPLICATION_SEEDS, tag="g10e", fixture="g10e_hier_posteriors_replication.json")
+    if a.few_experiments:
+        return few_experiments(a, dr, locs)
     if a.per_drug:
         drugs, channels = list(dr.drugs), list(dr.channels)
         chosen = []
@@ -249,6 +273,53 @@ def all_remaining(a, dr, locs, pairs=None, seeds=(301, 302), tag="g10c", fixture
                 write_fixture()
     n = write_fixture()
     print("%s written: %d pairs complete of %d in %.0f s" % (fixture, n, len(pairs), time.time() - t0))
+
+
+def few_experiments(a, dr, locs, fixture="g11_hier_posteriors_few_experiments.json"):
+    """G11: see the module docstring.  Runs are keyed by (drug, channel, Ne, seed); the scratch log g11_runs.jsonl makes it resumable."""
+    import make_golden as G
+    from pyhillfit_amd import bestfit
+    starts, seeds = {}, {}
+    for d, c, ne in FEW_EXPERIMENTS:
+        cut = [x for x in G.concat_pair(dr, d, c)["experiments"][:ne]]
+        assert len(cut) == ne
+        starts[(d, c, ne)] = np.asarray(bestfit.hierarchical_first_iteration(cut, locs), dtype=float)
+        seeds[(d, c, ne)] = FEW_EXPERIMENTS_SEEDS
+    log_path = os.path.join(HERE, "g11_runs.jsonl")
+    runs = []
+    if os.path.exists(log_path):
+        with open(log_path) as f:
+            runs = [json.loads(l) for l in f if l.strip()]
+    fixture_path = os.path.join(HERE, fixture)
+    if os.path.exists(fixture_path):
+        with open(fixture_path) as f:
+            known = {(r["drug"], r["channel"], r["Ne"], r["seed"]) for r in runs}
+            runs += [r for e in json.load(f) for r in e["runs"] if (r["drug"], r["channel"], r["Ne"], r["seed"]) not in known]
+    have = {(r["drug"], r["channel"], r["Ne"], r["seed"]) for r in runs}
+    jobs = [(d, c, s, a.iterations, a.thinning, starts[(d, c, ne)].tolist()) for d, c, ne in FEW_EXPERIMENTS for s in seeds[(d, c, ne)]
+            if (d, c, ne, s) not in have]
+    jobs.sort(key=lambda j: -len(j[5]))                   # Ne = 2 (the longer runs) first
+    print("g11: %d cases, %d runs to do (%d already there)" % (len(FEW_EXPERIMENTS), len(jobs), len(runs)), flush=True)
+    t0 = time.time()
+
+    def write_fixture():
+        out = []
+        for d, c, ne in FEW_EXPERIMENTS:
+            mine = sorted([r for r in runs if (r["drug"], r["channel"], r["Ne"]) == (d, c, ne)], key=lambda r: r["seed"])
+            if [r["seed"] for r in mine] == list(seeds[(d, c, ne)]):
+                out.append(_pool_entry(d, c, starts[(d, c, ne)].tolist(), mine, a.iterations, a.thinning))
+        with open(fixture_path, "w") as f:
+            json.dump(out, f, separators=(",", ":"))
+        return len(out)
+    with mp.get_context("fork").Pool(a.workers) as pool, open(log_path, "a") as log:
+        for k, r in enumerate(pool.imap_unordered(_run, jobs)):
+            r["Ne"] = (len(r["mean"]) - 6) // 2           # dim + 1 columns, dim = 5 + 2 Ne
+            runs.append(r)
+            log.write(json.dumps(r) + "\n"); log.flush()
+            print("  g11 %-14s %-12s Ne %d seed %d: acceptance %.3f, %.0f s (%.0f s elapsed, %d of %d)"
+                  % (r["drug"], r["channel"], r["Ne"], r["seed"], r["acceptance"], r["seconds"], time.time() - t0, k + 1, len(jobs)), flush=True)
+    n = write_fixture()
+    print("%s written: %d cases complete of %d in %.0f s" % (fixture, n, len(FEW_EXPERIMENTS), time.time() - t0))
 
 
 if __name__ == "__main__":

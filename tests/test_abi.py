@@ -95,6 +95,16 @@ def test_argument_validation_without_gpu(lib):
     assert lib.phf_hierarchical_advance_queued(C.byref(hp), C.byref(prob), C.byref(pr), C.byref(cfg), 0, 10, 1, None, None, 0, 0, None, None) == -1
     assert b"queue" in lib.phf_last_error()
     assert lib.phf_debug_isa(99, 1, 1, 1, None) == -1 and lib.phf_debug_isa(0, 0, None, None, None) == 0
+    # 1 <= Ne <= PHF_HIER_MAX_EXPTS = 64: init, advance and log-target refuse 0 and 65 experiments before any launch (as phf_hierarchical_state_size does)
+    prob.kernel_hint = 0
+    for bad_ne in (0, 65):
+        hb = H.HierPoints(1, 512, bad_ne, 0, 1, 1, 1)
+        assert lib.phf_hierarchical_init(C.byref(hb), C.byref(prob), C.byref(pr), 0.01, 1, 1, None, None) == -3, bad_ne
+        assert b"1..64 experiments" in lib.phf_last_error()
+        assert lib.phf_hierarchical_advance(C.byref(hb), C.byref(prob), C.byref(pr), C.byref(cfg), 0, 10, 1, None, None, 0, None) == -3, bad_ne
+        assert b"1..64 experiments" in lib.phf_last_error()
+        assert lib.phf_hierarchical_log_target(C.byref(hb), C.byref(pr), 1, 1, 1, 1, None) == -3, bad_ne
+        assert b"1..64 experiments" in lib.phf_last_error()
     # ABI 7: workspace sizes (no device call), the fused launch's checks
     lib.phf_hierarchical_queue_words.restype = C.c_int64
     prob.kernel_hint = 0

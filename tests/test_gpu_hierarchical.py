@@ -396,7 +396,7 @@ def test_generic_ne_kernel_bit_identical_to_cpu_twin(gpu, oracle_pair):
     assert np.isfinite(chain).all() and (np.diff(chain[:, 0, 0, :], axis=0) != 0).any()
 
 
-def _hier_posteriors_against_reference_loop(gpu, dr, fixture, C, seed, report_name, failures=None):
+def _hier_posteriors_against_reference_loop(gpu, dr, fixture, C, seed, report_name, failures=None, first_experiments=False):
     """every pair of a G10-style fixture: C chains from the fixture's start point, the reference's run length and burn-in, moments on
     the device; EVERY column's pooled mean within 1 % + 4 standard errors of the reference's (the larger of: batch means pooled over the
     seeds, scatter between the seeds), every pooled sd within 20 % + 4 standard errors of the reference's OWN pooled sd — the same form as
@@ -405,7 +405,8 @@ def _hier_posteriors_against_reference_loop(gpu, dr, fixture, C, seed, report_na
     [0.8, 1.2]; where each reference chain sits in its own corner of a flat direction (a steep experiment's Hill_i) or a rarely visited
     region carries part of the variance (Dofetilide-Cav1.2: 5 % of 512 GPU chains visit a low-pIC50_1 region that ten reference chains
     have not sampled in proportion; the MEDIAN chain's width is the reference's) r reaches 0.1 .. 0.2 —, acceptance within 0.02.  Returns the per-pair report.  failures: None =
-    assert pair by pair; a list = collect (pair, what) of everything outside instead, so that a big fixture reports ALL of it at once."""
+    assert pair by pair; a list = collect (pair, what) of everything outside instead, so that a big fixture reports ALL of it at once.
+    first_experiments (G11): an entry's pair is cut to its first e["Ne"] experiments, as the command line's -Ne does (PyHillFit.py:228-231)."""
     from pyhillfit_amd import hierarchical as H
     beyond_plain_band, columns_seen = [], [0]
     groups = {}
@@ -416,6 +417,8 @@ def _hier_posteriors_against_reference_loop(gpu, dr, fixture, C, seed, report_na
         T, thin = entries[0]["iterations"], entries[0]["thinning"]
         assert all(e["iterations"] == T and e["thinning"] == thin for e in entries) and T >= 300000
         exs = [dr.load_crumb_data(e["drug"], e["channel"])[2] for e in entries]
+        if first_experiments:
+            exs = [x[:ne] for x in exs]
         assert all(len(x) == ne for x in exs)
         s = H.HierarchicalSampler(H.PackedHierPoints(exs), list(range(len(exs))), C, thinning=thin, seed=seed, device=gpu)
         s.init(np.array([e["first_iteration"] for e in entries]), cov_scale=0.01)                   # PyHillFit.py:431

@@ -13,7 +13,7 @@ from scipy import stats as sst
 from scipy.special import ndtr, ndtri
 
 from conftest import REPO
-from test_gpu_waic import synthetic_points, synthetic_rows
+from test_gpu_waic import synthetic_pair, synthetic_points, synthetic_rows
 from test_waic_host import _pred, hier_loglik, sl_loglik
 
 pytestmark = pytest.mark.gpu
@@ -96,6 +96,9 @@ def _crumb_points(dr, ne=None):
     from pyhillfit_amd import waic as wc
     from pyhillfit_amd.PyHillFit import experiments_and_labels
     per, labels = [], []
+    if ne is not None and ne > 6:                     # more experiments than any Crumb pair has: three synthetic pairs of four points each
+        rng = np.random.default_rng(ne)
+        return wc.Points.hierarchical([synthetic_pair(rng, [4] * ne)[0] for _ in range(3)])
     for d in dr.drugs:
         for c in dr.channels:
             try:
@@ -118,7 +121,9 @@ def _theta(rng, kind, m, ne=None):
 
 
 # ---- 1. the replicate evaluator against the restatement -----------------------------------------------------------------------------
-@pytest.mark.parametrize("kind,ne", [(1, None), (2, None), ("hierarchical", 3), ("hierarchical", 4)])
+@pytest.mark.parametrize("kind,ne", [(1, None), (2, None), ("hierarchical", 3), ("hierarchical", 4),
+                                     ("hierarchical", 1), ("hierarchical", 2),         # every Crumb pair cut to its first experiment(s), as -Ne does
+                                     ("hierarchical", 9), ("hierarchical", 64)])       # synthetic pairs: no Crumb pair has that many (64 x 4 = 256 points)
 def test_replicate_against_restatement(gpu, dr_setup, kind, ne):
     from pyhillfit_amd import ppc as pp
     pts = _crumb_points(dr_setup, ne)

@@ -85,7 +85,7 @@ def test_accumulation_matches_restatement(gpu, kind, chains, counts, rows):
     check_against_restatement(pts, kind, x, run_stream(pts, kind, x, [7, 8], gpu), gpu)
 
 
-@pytest.mark.parametrize("ne", [3, 5, 6])
+@pytest.mark.parametrize("ne", [3, 5, 6, 1, 2, 9])
 def test_hierarchical_ne(gpu, ne):
     rng = np.random.default_rng(40 + ne)
     pts = synthetic_points(rng, [ne * 3, ne * 2 + 1], ne)

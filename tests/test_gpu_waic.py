@@ -83,6 +83,19 @@ def test_batch_single_level_all_crumb_pairs(gpu, dr_setup, model):
         assert np.sum(got[i, :n]) == pytest.approx(ident, rel=1e-11, abs=1e-9)
 
 
+def synthetic_pair(rng, sizes):
+    """(experiments, truth): one pair with len(sizes) experiments of sizes[i] points — a common (pIC50, Hill, sigma), a per-experiment
+    scatter of pIC50 and Hill, doses within 1.5 decades of the IC50, y = clip(Hill curve + sigma z, 0, 100)"""
+    pic50, hill, sigma = rng.uniform(4.0, 7.0), rng.uniform(0.7, 1.5), rng.uniform(3.0, 8.0)
+    expts = []
+    for n in sizes:
+        p_i, h_i = pic50 + rng.normal(0.0, 0.15), hill * np.exp(rng.normal(0.0, 0.1))
+        dose = 10.0 ** (6.0 - p_i + rng.uniform(-1.5, 1.5, n))
+        pred = 100.0 * (1.0 - 1.0 / (1.0 + (dose / 10.0 ** (6.0 - p_i)) ** h_i))
+        expts.append(np.column_stack([dose, np.clip(pred + sigma * rng.standard_normal(n), 0.0, 100.0)]))
+    return expts, (pic50, hill, sigma)
+
+
 def synthetic_points(rng, counts, ne=None):
     from pyhillfit_amd import waic as wc
     per = []
@@ -102,7 +115,7 @@ def synthetic_points(rng, counts, ne=None):
     return wc.Points.hierarchical(per) if ne else wc.Points.single_level(per)
 
 
-@pytest.mark.parametrize("ne", [3, 4, 5, 6])
+@pytest.mark.parametrize("ne", [3, 4, 5, 6, 1, 2, 8, 9, 64])        # the Crumb set's 3..6, then both ends of 1 <= Ne <= 64 and 8 | 9
 def test_batch_hierarchical(gpu, ne):
     from pyhillfit_amd import waic as wc
     rng = np.random.default_rng(ne)

@@ -325,3 +325,22 @@ def test_g10_and_g5d_fixtures_are_what_their_generators_say():
         g5c = [w for w in json.load(f) if (w["drug"], w["channel"]) == ("Ranolazine", "Nav1.5-peak")][0]
     assert abs(p[0] - g5c["mean"][0]) < 1e-9                        # seed 1 = the chain G5c holds ...
     assert np.mean(p >= p[0]) <= 0.10 and (p[0] - p[1:].mean()) / (p[1:].std(ddof=1) / np.sqrt(len(p) - 1)) > 3.0   # ... among the highest of the 96, far from their mean
+
+
+def test_g11_fixture_is_what_its_generator_says():
+    """G11 (make_golden_posteriors_hier.py --few-experiments): the first four G10 pairs cut to their first 1 and first 2 experiments — 8 cases in
+    that order —, seeds 501..508 for each, the reference's lifted loop (PyHillFit.py:431-511) at its own length, every column"""
+    with open(os.path.join(GOLDEN, "g11_hier_posteriors_few_experiments.json")) as f:
+        g11 = json.load(f)
+    assert [(e["drug"], e["channel"], e["Ne"]) for e in g11] == [(d, c, ne) for d, c in (("Amiodarone", "hERG"), ("Amiodarone", "Kv4.3"), ("Dofetilide", "hERG"),
+                                                                                       ("Amitriptyline", "Kv4.3")) for ne in (1, 2)]
+    for e in g11:
+        assert e["iterations"] == 500000 and e["thinning"] == 5 and e["dim"] == 5 + 2 * e["Ne"] == len(e["first_iteration"])
+        assert [r["seed"] for r in e["runs"]] == list(range(501, 509))
+        assert all(r["reference_lines"] == [[431, 511]] and r["rows"] == 75001 and r["Ne"] == e["Ne"] and 0.23 < r["acceptance"] < 0.27 for r in e["runs"])
+        means = np.array([r["mean"] for r in e["runs"]])
+        assert means.shape == (8, e["dim"] + 1) and np.isfinite(means).all()
+        assert np.allclose(e["pooled"]["mean"], means.mean(axis=0))
+    # a cut pair's start point is the start point of its first experiments alone: (pIC50_1, Hill_1) is shared by a pair's two cases
+    for one, two in zip(g11[0::2], g11[1::2]):
+        assert np.allclose(one["first_iteration"][4:6], two["first_iteration"][4:6], rtol=1e-9, atol=0)
