@@ -519,6 +519,32 @@ int phf_quantiles_accumulate_curves(const double* rows, int64_t num_rows, int nu
 int phf_quantiles_reduce(int num_problems, int num_columns, int curve_points, int bins, const double* probs, int num_probs,
                          const void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ---- dose-response bands of the hierarchical model ----------------------------------------------------------------------------
+ * (pyhillfit_amd/csrc/phf_hier_bands.h, phf_quantiles.hip; DESIGN.md §3, "Hierarchical bands").  Rows are the hierarchical sampler's:
+ * columns 0..3 = (alpha, beta, mu, s).  Per draw and dose the Hill curve, in percent, of
+ *   the inferred underlying effect    Hill = alpha, pIC50 = mu;
+ *   a predicted future experiment     Hill* = alpha exp(logit(u_H) / beta) (log-logistic), pIC50* = mu + s logit(u_P) (logistic),
+ *                                     u = (k + 1/2) 2^-52 from two words of the draw's block (k = (w_a >> 6) 2^26 + (w_b >> 6)),
+ * binned through the histograms above.  A workspace made with curve_points = 2 num_doses holds per problem the num_columns column
+ * slots, then num_doses underlying-effect slots, then num_doses future-experiment slots; phf_quantiles_workspace_bytes, _init,
+ * _accumulate (the columns) and _reduce serve it unchanged.  Random stream: one Philox block (the samplers' rounds) per draw,
+ * counter = (chain_id_base + chain, problem_id[q], first_row + r, 0xC0000000), key = seed: disjoint from the samplers, the posterior
+ * predictive checks and replica exchange, independent of how the rows are cut into calls (and of the dose: the doses of a draw
+ * share its (Hill*, pIC50*)).  A draw with a non-finite alpha, beta, mu or s, alpha <= 0 or beta <= 0 (and, future experiment,
+ * s <= 0) gives NaN: counted apart.
+ *   ln_doses       device [num_problems][num_doses], the natural log of each dose
+ *   problem_id     device [num_problems] uint32: the global problem number of each problem (the samplers' problem_id)
+ *   row_stride_cols >= 4; total_rows <= 2^32; the rest as phf_quantiles_accumulate_curves
+ * An invalid argument gives PHF_ERR_INVALID_ARGUMENT without touching a GPU (phf_last_error() says why). */
+int phf_quantiles_accumulate_hier_curves(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                                         const double* ln_doses, int num_columns, int num_doses, int bins, int64_t first_row,
+                                         int64_t total_rows, const uint32_t* problem_id, uint32_t chain_id_base, uint64_t seed,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+/* Batch evaluator: draw i at theta[.][i] = (alpha, beta, mu, s) ([4][m]) with the stream counter counter[i][0..2] = (chain id,
+ * problem id, row) and the key seed: out [m][2] = (Hill*, pIC50*); NaN, NaN for parameters that give no draw.  Serves the tests and
+ * the chain-file tool. */
+int phf_hier_band_draws(int64_t m, const double* theta, const uint32_t* counter, uint64_t seed, double* out, void* stream);
+
 /* ---- posterior predictive checks ----------------------------------------------------------------------------------------------
  * (pyhillfit_amd/csrc/phf_ppc.hip, phf_ppc.h; DESIGN.md §3, "Posterior predictive checks").  Points, likelihoods and rows as
  * phf_waic_*.  Per draw (a row of a chain) and point, one replicated response y_rep:

@@ -5,6 +5,7 @@
            [--num-chains 64 | 128 with --hierarchical] [--seed 25] [--device cuda:0] [--save-all-chains] [--segment 20000]
            [--diagnostics [--diagnostic-lags 256]] [--waic] [--loo [--loo-tail-per-chain 0]]
            [--quantiles [--quantile-probs 0.025,...,0.975] [--quantile-bins 16384] [--curve-bands G]] [--ppc]
+           [--hierarchical --quantiles --predictive-bands G [--band-concs c1,c2,...]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -17,7 +18,9 @@ accuracy of every data point over all chains (pyhillfit_amd/waic.py), accumulate
 k-hat of every data point (pyhillfit_amd/loo.py), accumulated the same way; with --quantiles, posterior quantiles and 90 / 95 %
 credible intervals of every column over all chains (pyhillfit_amd/quantiles.py), and with --curve-bands G the same of the
 dose-response curve at G doses, accumulated the same way; with --ppc, posterior predictive checks (test quantities of replicated
-data against the data, and the predictive PIT of every data point; pyhillfit_amd/ppc.py), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
+data against the data, and the predictive PIT of every data point; pyhillfit_amd/ppc.py), accumulated the same way; with
+--hierarchical --quantiles --predictive-bands G, the quantiles of the dose-response curve of the inferred underlying effect and of a
+predicted future experiment at G doses (and at the named --band-concs), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -65,6 +68,21 @@ def check_args(parser, args):
         parser.error("--curve-bands is single-level only (no bands for the hierarchical model)")
     if args.curve_bands and not args.quantiles:
         parser.error("--curve-bands needs --quantiles")
+    if args.predictive_bands < 0:
+        parser.error("--predictive-bands must be >= 1")
+    if args.predictive_bands and not args.hierarchical:
+        parser.error("--predictive-bands needs --hierarchical (single-level: --curve-bands)")
+    if args.predictive_bands and not args.quantiles:
+        parser.error("--predictive-bands needs --quantiles")
+    if args.band_concs is not None:
+        from .quantiles import parse_band_concs
+        if isinstance(args.band_concs, str):
+            try:
+                args.band_concs = parse_band_concs(args.band_concs)
+            except ValueError as e:
+                parser.error(str(e))
+        if not args.predictive_bands:
+            parser.error("--band-concs needs --predictive-bands")
 
 
 def build_parser():
@@ -115,6 +133,12 @@ def build_parser():
     new.add_argument("--curve-bands", type=int, default=0, metavar="G", help="--quantiles, single-level only: also the quantiles of the "
                      "dose-response curve at G doses log-spaced from the pair's smallest dose / 10 to its largest x 10; written to the "
                      "summary JSON as \"curve_band\"")
+    new.add_argument("--predictive-bands", type=int, default=0, metavar="G", help="--hierarchical --quantiles: the quantiles of the "
+                     "dose-response curve of the inferred underlying effect (Hill = alpha, pIC50 = mu) and of a predicted future experiment "
+                     "(Hill ~ log-logistic(alpha, beta), pIC50 ~ logistic(mu, s), one replicate per draw) at G doses log-spaced from the "
+                     "pair's smallest dose / 10 to its largest x 10; written to the summary JSON as \"hierarchical_bands\"")
+    new.add_argument("--band-concs", type=str, default=None, metavar="c1,c2,...", help="--predictive-bands: named concentrations (uM, "
+                     "all > 0, at most 64) appended after the grid (the reference's -c/--concs)")
     new.add_argument("--ppc", action='store_true', default=False, help="posterior predictive checks: mid-p values of the deviance, mean, sd "
                      "and counts of 0 and 100 of data replicated from every post-burn-in draw of every chain against the data's, and the "
                      "predictive PIT of every data point, accumulated on the GPU while the rows stream past; written to the summary JSON as \"ppc\"")

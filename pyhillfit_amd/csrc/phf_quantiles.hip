@@ -14,12 +14,17 @@
 //            all fall in one bin adds once), flushed to the uint64 counts in HBM with integer atomics for its non-zero bins only.
 // Integer counts are order-independent: the result is bit-identical whatever the launch shape, the arrival order or the row cuts.
 // A value that is not finite, or whose t is not (|x - a| beyond ~2^980 w0), is counted apart and never binned.
+// Hierarchical bands (phf_hier_bands.h): two more value sources read columns 0..3 (alpha, beta, mu, s) of a hierarchical row — the
+// curve of the inferred underlying effect (Hill = alpha, pIC50 = mu) and of a predicted future experiment (Hill*, pIC50* drawn by
+// inversion from the draw's own Philox block, addressed by the GLOBAL row index).  A value is a pure function of (problem, dose,
+// row, chain): prepare and bin each recompute it, D doses of one draw recompute the draw's block, two logits and one exp.
 // reduce: one workgroup per slot, a prefix sum over the bins; for each p the bin of the rank r = ceil(p N) draw (clamped to [1, N];
 // numpy's quantile(method="inverted_cdf")), its edges clamped to [min, max], and a value interpolated linearly by rank in the bin.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
+#include "phf_hier_bands.h"
 #include "phf_pointwise.h"
 
 namespace {
@@ -34,6 +39,8 @@ constexpr int kMinBins = 64, kMaxBins = 32768, kMaxProbs = 64;
 constexpr int64_t kValuesPerBlock = 131072;   // values one bin workgroup takes before a call's slot is split over more
 constexpr int kTargetBlocks = 4096;           // ... up to about this many bin workgroups per launch
 constexpr int64_t kMaxFlat = 0x7fffffff;      // rows x chains of one call: a 31-bit flat index
+constexpr int kUnderlying = 3, kFuture = 4;   // value sources after the column (0) and the single-level curves (1, 2)
+constexpr int kDrawThreads = 256;
 
 struct QArgs {
   const double* rows;             // [nr][Q][stride][C]
@@ -47,6 +54,9 @@ struct QArgs {
   unsigned long long* counts;     // [S][B]
   double* hdr;                    // [S][kHdr]
   unsigned long long* nonfinite;  // [S]
+  const uint32_t* problem_id;     // hierarchical bands: [Q], the global problem number of each problem
+  uint32_t chain_id_base, k0, k1; // ... and the stream's chain offset and key
+  uint32_t first_row;             // ... and the global index of rows[0]
 };
 
 struct QReduceArgs {
@@ -58,12 +68,18 @@ struct QReduceArgs {
   double* out;                    // [S][kOutHead + kOutPerProb P]
 };
 
-// value i (= row * C + chain) of launch column k of problem q: a column of the rows (MODEL 0) or the Hill curve of model MODEL at dose k
+// value i (= row * C + chain) of launch column k of problem q: a column of the rows (MODEL 0), the Hill curve of model MODEL at dose k
+// (1, 2), or the hierarchical model's curve at dose k of the underlying effect (3) / of a future experiment (4): count doses each
 template <int MODEL>
-__device__ inline double q_value(const QArgs& a, int q, int k, unsigned i, phf_ktab k_exp) {
+__device__ inline double q_value(const QArgs& a, int q, int k, unsigned i, phf_ktab k_exp, phf_ktab k_log) {
   const unsigned r = i / (unsigned)a.C, c = i - r * (unsigned)a.C;
   const double* x = a.rows + ((size_t)r * a.Q + q) * a.stride * (size_t)a.C + c;
   if (MODEL == 0) return x[(size_t)(a.first + k) * a.C];
+  if (MODEL >= kUnderlying) {
+    const size_t C = (size_t)a.C;
+    return phf_band_value_k(MODEL == kFuture ? PHF_BAND_FUTURE : PHF_BAND_UNDERLYING, a.ln_dose[(size_t)q * a.count + k], x[0], x[C], x[2 * C],
+                            x[3 * C], a.chain_id_base + c, a.problem_id[q], a.first_row + r, a.k0, a.k1, k_exp, k_log);
+  }
   const double pic50 = x[0], hill = MODEL == 2 ? x[a.C] : 1.0;
   if (!__builtin_isfinite(pic50) || !__builtin_isfinite(hill)) return PHF_NAN;
   return phf_pw_pred(MODEL, a.ln_dose[(size_t)q * a.G + k], hill, PHF_LN10 * (6.0 - pic50), k_exp);
@@ -76,13 +92,30 @@ __device__ inline bool q_holds(double tmin, double tmax, int k, int B) {
   return __builtin_floor(__builtin_ldexp(tmin, -k)) >= -(double)(B / 2) && __builtin_floor(__builtin_ldexp(tmax, -k)) < (double)(B / 2);
 }
 
-// the 2^(j/64) table of phf_exp_* into LDS (the Hill curve needs no other table)
-__device__ inline void load_exp_table() {
+// the 2^(j/64) table of phf_exp_* into LDS (the Hill curve needs no other table); the future experiment's draws take logarithms: the log table too
+template <int MODEL>
+__device__ inline void load_tables() {
 #if defined(__HIP_DEVICE_COMPILE__)
-  for (int i = threadIdx.x; i < 64; i += blockDim.x) phf_lds_exp2[i] = phf_t_exp2[i];
-  __syncthreads();
+  if (MODEL == kFuture) {
+    PHF_MATH_TABLES_TO_LDS();
+  } else if (MODEL != 0) {
+    for (int i = threadIdx.x; i < 64; i += blockDim.x) phf_lds_exp2[i] = phf_t_exp2[i];
+    __syncthreads();
+  }
 #endif
 }
+
+// the log polynomial in vector registers where the value source takes logarithms (PHF_KFETCH_V), nothing otherwise
+#define Q_KFETCH_LOG(name)                                          \
+  double name##_buf[PHF_K_LOG_N];                                   \
+  if (MODEL == kFuture) {                                           \
+    PHF_UNROLL                                                      \
+    for (int phf_i_ = 0; phf_i_ < PHF_K_LOG_N; ++phf_i_) {          \
+      name##_buf[phf_i_] = phf_k_log[phf_i_];                       \
+      asm volatile("" : "+v"(name##_buf[phf_i_]));                  \
+    }                                                               \
+  }                                                                 \
+  const phf_ktab name = name##_buf
 
 // block reductions through a small LDS array (blockDim.x <= 1024: 16 wavefronts)
 __device__ inline double block_min(double v, double* sh) {
@@ -117,8 +150,9 @@ __global__ __launch_bounds__(kPrepThreads) void q_prepare_kernel(const QArgs a) 
   __shared__ double s_red[16];
   __shared__ unsigned s_redu[16];
   __shared__ int s_level[2];
-  if (MODEL != 0) load_exp_table();
+  load_tables<MODEL>();
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
+  Q_KFETCH_LOG(k_log);
   const int q = blockIdx.x / a.count, k = blockIdx.x % a.count;
   const size_t s = (size_t)q * a.spp + a.first + k;
   double* h = a.hdr + s * kHdr;
@@ -126,11 +160,11 @@ __global__ __launch_bounds__(kPrepThreads) void q_prepare_kernel(const QArgs a) 
   if (h[5] == 0.0) {                                           // not anchored yet: the first finite value in (row, chain) order
     unsigned best = 0xffffffffu;
     for (unsigned i = tid; i < a.n; i += kPrepThreads)
-      if (__builtin_isfinite(q_value<MODEL>(a, q, k, i, k_exp))) { best = i; break; }
+      if (__builtin_isfinite(q_value<MODEL>(a, q, k, i, k_exp, k_log))) { best = i; break; }
     best = block_min_u(best, s_redu);
     if (best == 0xffffffffu) return;                           // nothing finite yet: the bin pass counts every value apart
     if (tid == 0) {
-      const double x = q_value<MODEL>(a, q, k, best, k_exp);
+      const double x = q_value<MODEL>(a, q, k, best, k_exp, k_log);
       const double m = __builtin_fmax(__builtin_fabs(x), 0x1p-30);
       h[0] = x;
       h[1] = __builtin_ldexp(1.0, __builtin_amdgcn_frexp_exp(m) - 41);   // frexp exponent - 1 = floor(log2 m)
@@ -141,7 +175,7 @@ __global__ __launch_bounds__(kPrepThreads) void q_prepare_kernel(const QArgs a) 
   const double anchor = h[0], inv_w0 = 1.0 / h[1];             // a power of two: exact
   double lo = PHF_INF, hi = -PHF_INF;
   for (unsigned i = tid; i < a.n; i += kPrepThreads) {
-    const double x = q_value<MODEL>(a, q, k, i, k_exp);
+    const double x = q_value<MODEL>(a, q, k, i, k_exp, k_log);
     if (__builtin_isfinite(q_t(x, anchor, inv_w0))) { lo = __builtin_fmin(lo, x); hi = __builtin_fmax(hi, x); }
   }
   lo = block_min(lo, s_red);
@@ -179,8 +213,9 @@ __global__ __launch_bounds__(kPrepThreads) void q_prepare_kernel(const QArgs a) 
 template <int MODEL>
 __global__ __launch_bounds__(kBinThreads) void q_bin_kernel(const QArgs a) {
   extern __shared__ unsigned s_hist[];                          // [B]
-  if (MODEL != 0) load_exp_table();
+  load_tables<MODEL>();
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
+  Q_KFETCH_LOG(k_log);
   const int split = blockIdx.x % a.splits;
   const int slot = blockIdx.x / a.splits;
   const int q = slot / a.count, k = slot % a.count;
@@ -197,7 +232,7 @@ __global__ __launch_bounds__(kBinThreads) void q_bin_kernel(const QArgs a) {
   unsigned nf = 0;
   const int lane = __lane_id();
   for (unsigned i = i0 + tid; i < i1; i += kBinThreads) {
-    const double x = q_value<MODEL>(a, q, k, i, k_exp);
+    const double x = q_value<MODEL>(a, q, k, i, k_exp, k_log);
     int j = -1;
     if (anchored) {
       const double t = q_t(x, anchor, inv_w0);
@@ -282,6 +317,21 @@ __global__ __launch_bounds__(kReduceThreads) void q_reduce_kernel(const QReduceA
     double* op = o + kOutHead + kOutPerProb * p;
     op[0] = v; op[1] = lo; op[2] = hi; op[3] = (double)j;
   }
+}
+
+// ---- batch evaluator of the band draws ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kDrawThreads) void hier_band_draws_kernel(int64_t m, const double* theta, const uint32_t* counter, uint32_t k0,
+                                                                       uint32_t k1, double* out) {
+  PHF_MATH_TABLES_TO_LDS();
+  const int64_t i = (int64_t)blockIdx.x * kDrawThreads + threadIdx.x;
+  if (i >= m) return;
+  PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
+  PHF_KFETCH_V(k_log, phf_k_log, PHF_K_LOG_N);
+  double hill, pic50;
+  phf_band_future_k(theta[i], theta[m + i], theta[2 * m + i], theta[3 * m + i], counter[3 * i], counter[3 * i + 1], counter[3 * i + 2], k0,
+                    k1, k_exp, k_log, &hill, &pic50);
+  out[2 * i] = hill;
+  out[2 * i + 1] = pic50;
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
@@ -445,6 +495,43 @@ extern "C" int phf_quantiles_accumulate_curves(const double* rows, int64_t num_r
   QArgs a = args_of(rows, num_rows, num_problems, row_stride_cols, num_chains, num_columns, curve_points, bins, workspace);
   a.ln_dose = ln_doses; a.first = num_columns; a.count = curve_points;
   return model == 1 ? launch<1>(a, stream) : launch<2>(a, stream);
+}
+
+extern "C" int phf_quantiles_accumulate_hier_curves(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols,
+                                                    int num_chains, const double* ln_doses, int num_columns, int num_doses, int bins,
+                                                    int64_t first_row, int64_t total_rows, const uint32_t* problem_id,
+                                                    uint32_t chain_id_base, uint64_t seed, void* workspace, size_t workspace_bytes,
+                                                    void* stream) {
+  static const char* who = "phf_quantiles_accumulate_hier_curves";
+  if (num_doses < 1 || num_doses > (1 << 20))
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_hier_curves: num_doses must be in [1, 2^20]");
+  const int curve_points = 2 * num_doses;
+  int rc = check_geometry(who, num_problems, num_columns, curve_points, bins);
+  if (rc != PHF_OK) return rc;
+  if (!ln_doses) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_hier_curves: null ln_doses");
+  if (!problem_id) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_hier_curves: null problem_id");
+  if ((rc = check_rows(who, rows, num_rows, row_stride_cols, num_chains, 4, first_row, total_rows)) != PHF_OK) return rc;
+  if (total_rows > 4294967296LL)
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT,
+                    "phf_quantiles_accumulate_hier_curves: total_rows must fit the 32-bit row word of the random stream");
+  if ((rc = check_workspace(who, workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins))) != PHF_OK) return rc;
+  if (num_rows == 0) return PHF_OK;
+  QArgs a = args_of(rows, num_rows, num_problems, row_stride_cols, num_chains, num_columns, curve_points, bins, workspace);
+  a.ln_dose = ln_doses; a.problem_id = problem_id; a.chain_id_base = chain_id_base;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.first_row = (uint32_t)first_row;
+  a.first = num_columns; a.count = num_doses;
+  if ((rc = launch<kUnderlying>(a, stream)) != PHF_OK) return rc;
+  a.first = num_columns + num_doses;
+  return launch<kFuture>(a, stream);
+}
+
+extern "C" int phf_hier_band_draws(int64_t m, const double* theta, const uint32_t* counter, uint64_t seed, double* out, void* stream) {
+  if (m < 0 || (m > 0 && (!theta || !counter || !out)))
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_hier_band_draws: m must be >= 0 and the arrays non-null");
+  if (m == 0) return PHF_OK;
+  hipLaunchKernelGGL(hier_band_draws_kernel, dim3((unsigned)((m + kDrawThreads - 1) / kDrawThreads)), dim3(kDrawThreads), 0,
+                     static_cast<hipStream_t>(stream), m, theta, counter, (uint32_t)seed, (uint32_t)(seed >> 32), out);
+  return phf_check_launch("phf_hier_band_draws");
 }
 
 extern "C" int phf_quantiles_reduce(int num_problems, int num_columns, int curve_points, int bins, const double* probs, int num_probs,

@@ -538,8 +538,15 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         quant = None
         if getattr(args, "quantiles", False):                          # posterior quantiles over all chains, accumulated like the diagnostics
             from . import quantiles as qn
-            qn.check_memory(qn.workspace_bytes(Q, d + 1, 0, args.quantile_bins), device)
-            quant = qn.PosteriorQuantiles(Q, C, d + 1, saved_iterations - burn, args.quantile_probs, args.quantile_bins, device)
+            G = getattr(args, "predictive_bands", 0)
+            named = tuple(getattr(args, "band_concs", None) or ())
+            # the doses of the bands: G over the concentrations of the pair's fitted experiments, then the named ones
+            doses = [qn.band_doses(np.concatenate([np.asarray(e)[:, 0] for e in m[2]]), G, named) for m in members] if G else None
+            qn.check_memory(qn.workspace_bytes(Q, d + 1, 2 * (G + len(named)) if G else 0, args.quantile_bins), device)
+            quant = qn.PosteriorQuantiles(Q, C, d + 1, saved_iterations - burn, args.quantile_probs, args.quantile_bins, device,
+                                          band_ln_doses=np.log(np.array(doses)) if G else None, seed=args.seed,
+                                          problem_ids=[m[3] for m in members], chain_id_base=0)
+            quant.doses = doses
             if burn == 0:
                 quant.accumulate(s.row0.unsqueeze(0).contiguous())
         ppc = None
@@ -634,6 +641,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     loo_names, loo_parts = [], []
     quant_names, quant_parts = [], []
     ppc_names, ppc_parts = [], []
+    band_nf = 0
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
         Q, C = len(members), args.num_chains
@@ -685,7 +693,12 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                 from . import quantiles as qn
                 summ["quantiles"] = qn.json_record(quant_res, q, hierarchical_columns(ne), args.quantile_bins)
                 quant_names.append("{} + {}".format(d_clean, c_clean))
-                quant_parts.append((quant_res["bin_width"][q], quant_res["min"][q], quant_res["max"][q], quant_res["non_finite"][q]))
+                nc = int(quant_res["columns"])                          # the band slots follow the columns
+                quant_parts.append((quant_res["bin_width"][q, :nc], quant_res["min"][q, :nc], quant_res["max"][q, :nc],
+                                    quant_res["non_finite"][q, :nc]))
+                if run["quant"].doses is not None:
+                    summ["hierarchical_bands"] = qn.hier_band_record(quant_res, q, run["quant"].doses[q], args.predictive_bands)
+                    band_nf += int(np.sum(quant_res["non_finite"][q, nc:]))
             if ppc_res is not None:
                 from . import ppc as pp
                 summ["ppc"] = pp.json_record(ppc_res[q], run["ppc"].points, q)
@@ -706,7 +719,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         print(lo.report_line(rank, loo_names, loo_parts))
     if getattr(args, "quantiles", False):
         from . import quantiles as qn
-        print(qn.report_line(rank, quant_names, quant_parts))
+        print(qn.report_line(rank, quant_names, quant_parts, band_nf if getattr(args, "predictive_bands", 0) else None))
     if getattr(args, "ppc", False):
         from . import ppc as pp
         print(pp.report_line(rank, ppc_names, ppc_parts))

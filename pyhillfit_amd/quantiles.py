@@ -13,7 +13,11 @@ the inverse empirical CDF, numpy's quantile(method="inverted_cdf") — and repor
 hold the exact sample quantile, and a value interpolated linearly by rank inside the bin.  Non-finite draws are counted apart.
 
 Curve bands (single-level model 1 or 2): per draw the Hill curve 100 (1 - 1/(1 + exp(Hill (ln c - ln IC50)))) at G doses of the
-pair, binned as G more columns through the same histograms; the curve is never written to memory."""
+pair, binned as G more columns through the same histograms; the curve is never written to memory.
+
+Hierarchical bands (band_ln_doses): per draw (alpha, beta, mu, s) of a hierarchical row and per dose, the curve of the inferred
+underlying effect (Hill = alpha, pIC50 = mu) and of a predicted future experiment (Hill* ~ log-logistic(alpha, beta), pIC50* ~
+logistic(mu, s), drawn by inversion from the draw's own Philox block: csrc/phf_hier_bands.h), binned as 2 D more columns."""
 import ctypes as C
 
 import numpy as np
@@ -30,6 +34,12 @@ INTERVALS = {"ci90": (0.05, 0.95), "ci95": (0.025, 0.975)}
 METHOD = ("inverse empirical CDF (numpy quantile method='inverted_cdf': the ceil(p N)-th smallest draw) over all chains' post-burn-in "
           "draws, from an exact-count histogram of B bins whose grid is anchored at the first draw and coarsened by powers of two to "
           "hold [min, max]: [lo, hi] is the bin holding that draw, value is linear in rank inside it")
+BAND_METHOD = ("percent block 100 (1 - 1/(1 + exp(Hill (ln c - ln IC50)))) per post-burn-in draw (alpha, beta, mu, s) of every chain; "
+               "underlying: Hill = alpha, pIC50 = mu; future_experiment: one replicate per draw by inversion, Hill* = alpha exp(logit(u_H) / "
+               "beta) (log-logistic(scale alpha, shape beta)), pIC50* = mu + s logit(u_P) (logistic(mu, s)), u = (k + 1/2) 2^-52 with k = "
+               "(w_a >> 6) 2^26 + (w_b >> 6) from words (0, 1) (Hill) and (2, 3) (pIC50) of the Philox4x32 block (the samplers' rounds) "
+               "counter = (chain_id_base + chain, problem id, post-burn-in row index, 0xC0000000), key = seed; quantiles per dose: " + METHOD)
+MAX_BAND_CONCS = 64
 
 
 def parse_probs(text):
@@ -63,6 +73,19 @@ def curve_doses(concs, points):
     return np.logspace(np.log10(c.min() / 10.0), np.log10(c.max() * 10.0), int(points))
 
 
+def parse_band_concs(text):
+    """'0.1,10' -> tuple of concentrations in uM, all > 0 and finite, at most 64 (raises ValueError)"""
+    concs = tuple(float(v) for v in str(text).split(",") if v.strip())
+    if not concs or len(concs) > MAX_BAND_CONCS or not all(np.isfinite(c) and c > 0.0 for c in concs):
+        raise ValueError("--band-concs must be 1 to %d concentrations in uM, all > 0, got %r" % (MAX_BAND_CONCS, text))
+    return concs
+
+
+def band_doses(concs, points, named=()):
+    """the doses of a hierarchical band: the G grid doses of curve_doses, then the named concentrations"""
+    return np.concatenate([curve_doses(concs, points), np.asarray(named, dtype=np.float64)])
+
+
 def hill_curve(model, ln_dose, pic50, hill):
     """the curve the device bins, in numpy: 100 (1 - 1/(1 + exp(Hill (ln c - ln IC50)))), exp's argument capped at 40 as the
     targets cap it (model 1: Hill = 1)"""
@@ -75,10 +98,13 @@ class PosteriorQuantiles(object):
     """Streaming quantiles of num_problems x columns over `chains` chains and total_rows post-burn-in rows; with curve_ln_doses
     ([num_problems][G], natural log of the doses) and model 1 | 2 also the Hill curve at G doses per problem.
     accumulate() takes the rows in order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride][chains]
-    (asynchronous, on the current stream); result() reduces."""
+    (asynchronous, on the current stream); result() reduces.
+    Hierarchical bands: with band_ln_doses ([num_problems][D]) the rows are hierarchical ones and, per problem, D slots of the
+    underlying effect and D of a future experiment follow the columns; the future experiment's stream is addressed by seed,
+    problem_ids ([num_problems], the samplers' global problem ids) and chain_id_base."""
 
     def __init__(self, num_problems, chains, columns, total_rows, probs=DEFAULT_PROBS, bins=DEFAULT_BINS, device="cuda",
-                 curve_ln_doses=None, model=None):
+                 curve_ln_doses=None, model=None, band_ln_doses=None, seed=0, problem_ids=None, chain_id_base=0):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -95,6 +121,20 @@ class PosteriorQuantiles(object):
                 raise ValueError("curve_ln_doses must be [num_problems][G]")
             self.G, self.model = ld.shape[1], int(model)
             self.ln_doses = torch.from_numpy(ld).to(self.device)
+        self.D, self.problem_id = 0, None
+        if band_ln_doses is not None:
+            if curve_ln_doses is not None:
+                raise ValueError("single-level curve bands and hierarchical bands do not share a workspace")
+            ld = np.ascontiguousarray(band_ln_doses, dtype=np.float64)
+            if ld.ndim != 2 or ld.shape[0] != self.Q or ld.shape[1] < 1:
+                raise ValueError("band_ln_doses must be [num_problems][D], D >= 1")
+            ids = np.arange(self.Q) if problem_ids is None else np.asarray(problem_ids, dtype=np.int64)
+            if ids.shape != (self.Q,):
+                raise ValueError("problem_ids must name every problem")
+            self.D, self.G = ld.shape[1], 2 * ld.shape[1]
+            self.seed, self.chain_id_base = int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_id_base) & 0xFFFFFFFF
+            self.ln_doses = torch.from_numpy(ld).to(self.device)
+            self.problem_id = torch.from_numpy((ids & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).to(self.device)
         self.nbytes = workspace_bytes(self.Q, self.cols, self.G, self.B)
         self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
         _lib.check(self.lib.phf_quantiles_init(self.Q, self.cols, self.G, self.B, _ptr(self.ws), C.c_size_t(self.nbytes),
@@ -103,8 +143,9 @@ class PosteriorQuantiles(object):
 
     def accumulate(self, rows):
         """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.cols, self.C, tuple(rows.shape)))
+        need = max(self.cols, 4 if self.D else 0)
+        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < need:
+            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, need, self.C, tuple(rows.shape)))
         if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
             raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
         n = rows.shape[0]
@@ -120,7 +161,13 @@ class PosteriorQuantiles(object):
                 _lib.check(self.lib.phf_quantiles_accumulate(_ptr(part), m, self.Q, rows.shape[2], self.C, self.cols, self.G, self.B,
                                                              self.rows_seen, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
                                                              _stream_ptr(self.device)), "phf_quantiles_accumulate")
-            if self.G:
+            if self.D:
+                _lib.check(self.lib.phf_quantiles_accumulate_hier_curves(_ptr(part), m, self.Q, rows.shape[2], self.C, _ptr(self.ln_doses),
+                                                                         self.cols, self.D, self.B, self.rows_seen, self.N,
+                                                                         _ptr(self.problem_id), self.chain_id_base, self.seed,
+                                                                         _ptr(self.ws), C.c_size_t(self.nbytes),
+                                                                         _stream_ptr(self.device)), "phf_quantiles_accumulate_hier_curves")
+            elif self.G:
                 _lib.check(self.lib.phf_quantiles_accumulate_curves(_ptr(part), m, self.Q, rows.shape[2], self.C, self.model,
                                                                     _ptr(self.ln_doses), self.cols, self.G, self.B, self.rows_seen,
                                                                     self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
@@ -151,13 +198,17 @@ class PosteriorQuantiles(object):
         red = self.reduced()
         P = len(self.probs)
         per = red[..., HEAD:].reshape(self.Q, self.cols + self.G, P, PER_PROB)
-        return {"min": red[..., 0], "max": red[..., 1], "draws": red[..., 2], "non_finite": red[..., 3], "bin_width": red[..., 4],
-                "level": red[..., 5], "value": per[..., 0], "lo": per[..., 1], "hi": per[..., 2], "bin": per[..., 3],
-                "probs": np.array(self.probs), "columns": self.cols, "curve_points": self.G}
+        res = {"min": red[..., 0], "max": red[..., 1], "draws": red[..., 2], "non_finite": red[..., 3], "bin_width": red[..., 4],
+               "level": red[..., 5], "value": per[..., 0], "lo": per[..., 1], "hi": per[..., 2], "bin": per[..., 3],
+               "probs": np.array(self.probs), "columns": self.cols, "curve_points": self.G}
+        if self.D:
+            res.update(band_doses=self.D, seed=self.seed)
+        return res
 
     def free(self):
         self.ws = None
         self.ln_doses = None
+        self.problem_id = None
 
 
 def quantiles_of_draws(draws, probs=DEFAULT_PROBS, bins=DEFAULT_BINS, device="cuda"):
@@ -233,8 +284,52 @@ def curve_band_record(res, q, doses):
     return rec
 
 
-def report_line(rank, names, parts):
-    """one line per rank: pairs, the widest bin relative to its column's range, non-finite draws.
+def _band_part(res, q, first, count):
+    per = [column_record(res, q, first + g) for g in range(count)]
+    rec = {}
+    for k in ("value", "lo", "hi", "min", "max", "bin_width", "non_finite"):
+        rec[k] = [p[k] for p in per]
+    for k in INTERVALS:
+        if k in per[0]:
+            rec[k] = [p[k] for p in per]
+    return rec
+
+
+def hier_band_record(res, q, doses, n_grid):
+    """the "hierarchical_bands" object of problem q: the doses (uM; n_grid grid doses, then the named concentrations) and, per dose,
+    the quantiles (percent block) of the inferred underlying effect and of a predicted future experiment"""
+    c0, D = int(res["columns"]), int(res["band_doses"])
+    doses = [float(d) for d in doses]
+    if len(doses) != D or not 0 <= int(n_grid) <= D:
+        raise ValueError("%d doses, %d of them on the grid, for a band of %d" % (len(doses), n_grid, D))
+    return {"doses": doses, "probs": [float(p) for p in res["probs"]], "grid_points": int(n_grid),
+            "named_concentrations": doses[int(n_grid):], "seed": int(res["seed"]), "method": BAND_METHOD,
+            "underlying": _band_part(res, q, c0, D), "future_experiment": _band_part(res, q, c0 + D, D)}
+
+
+def hier_band_draws(theta, counters, seed, device="cuda"):
+    """(Hill*, pIC50*) [m][2] of m draws: theta [m][4] = (alpha, beta, mu, s), counters [m][3] = (chain id, problem id, row) of the
+    stream (phf_hier_band_draws); NaN where the parameters give no draw"""
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("hier_band_draws runs on a GPU device, not %s" % dev)
+    th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(-1, 4).T)
+    ct = np.ascontiguousarray(np.asarray(counters, dtype=np.int64).reshape(-1, 3) & 0xFFFFFFFF).astype(np.uint32)
+    m = th.shape[1]
+    if ct.shape[0] != m:
+        raise ValueError("one counter per draw")
+    t_th = torch.from_numpy(th).to(dev)
+    t_ct = torch.from_numpy(ct.view(np.int32)).to(dev)
+    out = torch.empty((m, 2), dtype=torch.float64, device=dev)
+    _lib.check(lib.phf_hier_band_draws(m, _ptr(t_th), _ptr(t_ct), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _stream_ptr(dev)),
+               "phf_hier_band_draws")
+    return out.cpu().numpy()
+
+
+def report_line(rank, names, parts, band_non_finite=None):
+    """one line per rank: pairs, the widest bin relative to its column's range, non-finite draws (and, with hierarchical bands,
+    band_non_finite: the non-finite band draws).
     parts: per problem (bin_width [cols], min [cols], max [cols], non_finite [cols])"""
     if len(names) == 0:
         return "quantiles [rank %d]: no problems" % rank
@@ -245,7 +340,10 @@ def report_line(rank, names, parts):
         if np.any(ok):
             rel = max(rel, float(np.max(np.asarray(w)[ok] / span[ok])))
         nf += int(np.sum(n))
-    return ("quantiles [rank {}]: {} pairs; widest bin {:.2e} of its column's range; {} non-finite draws".format(rank, len(names), rel, nf))
+    line = "quantiles [rank {}]: {} pairs; widest bin {:.2e} of its column's range; {} non-finite draws".format(rank, len(names), rel, nf)
+    if band_non_finite is not None:
+        line += "; {} non-finite band draws".format(int(band_non_finite))
+    return line
 
 
 def check_memory(nbytes, device, what="--quantiles"):
