@@ -442,6 +442,13 @@ int phf_waic_init(int num_problems, int stride, int num_chains, int64_t total_ro
 int phf_waic_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
                         int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, double* workspace,
                         size_t workspace_bytes, void* stream);
+/* The same accumulator with a GIVEN log-likelihood (likelihood code 4 of the streaming kernels): l of point p < count[q] of problem q
+ * is column p of the row, rows [num_rows][num_problems][row_stride_cols >= stride][num_chains]; of pts only stride and count are
+ * read (the other arrays must still be non-null).  Workspace, init and reduce are phf_waic_*'s.  Serves the integrated
+ * leave-one-experiment-out, whose "points" are the experiments. */
+int phf_waic_accumulate_given(const phf_pointwise_points* pts, const double* rows, int64_t num_rows, int num_problems, int row_stride_cols,
+                              int num_chains, int64_t first_row, int64_t total_rows, double* workspace, size_t workspace_bytes,
+                              void* stream);
 int phf_waic_reduce(int num_problems, int stride, int num_chains, int64_t total_rows, const double* workspace, size_t workspace_bytes,
                     double* out, void* stream);
 
@@ -485,6 +492,10 @@ int phf_psis_accumulate(const phf_pointwise_points* pts, int likelihood, int num
                         double* workspace, size_t workspace_bytes, void* stream);
 int phf_psis_reduce(const phf_pointwise_points* pts, int num_problems, int num_chains, int64_t total_rows, int tail_per_chain,
                     double* workspace, size_t workspace_bytes, double* out, double* tail_out, void* stream);
+/* phf_psis_accumulate with a GIVEN log-likelihood, as phf_waic_accumulate_given: l of point p is column p of the row. */
+int phf_psis_accumulate_given(const phf_pointwise_points* pts, const double* rows, int64_t num_rows, int num_problems, int row_stride_cols,
+                              int num_chains, int64_t first_row, int64_t total_rows, int tail_per_chain, double* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ---- posterior quantiles and curve bands -------------------------------------------------------------------------------------
  * Exact-count histograms of every (problem, column) over all chains' draws, streamed like the diagnostics
@@ -544,6 +555,36 @@ int phf_quantiles_accumulate_hier_curves(const double* rows, int64_t num_rows, i
  * problem id, row) and the key seed: out [m][2] = (Hill*, pIC50*); NaN, NaN for parameters that give no draw.  Serves the tests and
  * the chain-file tool. */
 int phf_hier_band_draws(int64_t m, const double* theta, const uint32_t* counter, uint64_t seed, double* out, void* stream);
+
+/* ---- marginal log-likelihood of whole experiments (integrated leave-one-experiment-out) -------------------------------------
+ * (pyhillfit_amd/csrc/phf_hier_marginal.hip, phf_hier_marginal.h; DESIGN.md §3, "Integrated leave-one-experiment-out").  For a draw
+ * phi = (alpha, beta, mu, s, sigma) = columns 0..3 and 4 + 2 num_expts of a hierarchical vector and experiment e (the points of pts
+ * with tag == e, hierarchical points as for phf_waic_*), m_e = ln of the integral of the experiment's truncated-normal likelihood
+ * over Hill ~ log-logistic(alpha, beta), pIC50 ~ logistic(mu, s) on pIC50 >= -2 (not renormalised for the bound), by the fixed
+ * num_nodes x num_nodes rule of phf_hier_marginal.h, and g_e = |m_e - m_e of the even-even nodes|, the rule's own error estimate.
+ *   nodes       device [3][num_nodes] doubles: x_k, ln w_k, ln w_k of the even nodes (pyhillfit_amd/marginal.py: node_table);
+ *               num_nodes is 32, 64, 128 or 256
+ *   sigma <= 1e-3 gives m = -inf, g = 0; parameters that are not finite, alpha, beta or s <= 0, or a problem index out of range
+ *   give NaN, NaN.  An experiment without points gives m = ln of the mass of the nodes with pIC50 >= -2.
+ * num_expts is 1..64; at most 512 points per problem (stride).  One wavefront per (draw, experiment), no atomics: bit-identical to
+ * the host build of phf_hier_marginal.h.  An invalid argument gives PHF_ERR_INVALID_ARGUMENT without touching a GPU
+ * (phf_last_error() says why). */
+/* Batch evaluator: theta [5 + 2 num_expts][m], problem_index [m]; out [2][m][num_expts] = m_e, then g_e.  Serves the tests and the
+ * chain-file tool. */
+int phf_hier_marginal_loglik(const phf_pointwise_points* pts, int num_expts, const double* nodes, int num_nodes, int64_t m,
+                             const int32_t* problem_index, const double* theta, double* out, void* stream);
+/* the number of rows r in [first_row, first_row + num_rows) with r mod every == 0 (-1 for an invalid argument) */
+int64_t phf_hier_marginal_rows_used(int64_t first_row, int64_t num_rows, int every);
+/* Streaming: rows device [num_rows][num_problems][row_stride_cols][num_chains] (the hierarchical sampler's row buffer or a slice of
+ * it), rows[0] being global post-burn-in row first_row.  Exactly the global rows r with r mod every == 0 are used, however the calls
+ * cut the rows: with U = phf_hier_marginal_rows_used(first_row, num_rows, every),
+ *   loglik, gap   device [U][num_problems][num_expts][num_chains]: m_e and g_e of the call's used rows, in row order
+ *   gap_max       device [num_problems][num_expts][num_chains]: the running per-chain maximum of g_e, updated in place (the caller
+ *                 zeroes it before the first call; NaN gaps are passed over; the chains are the caller's to fold, a maximum
+ *                 has no rounding) */
+int phf_hier_marginal_rows(const phf_pointwise_points* pts, int num_expts, const double* nodes, int num_nodes, const double* rows,
+                           int64_t num_rows, int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int every,
+                           double* loglik, double* gap, double* gap_max, void* stream);
 
 /* ---- posterior predictive checks ----------------------------------------------------------------------------------------------
  * (pyhillfit_amd/csrc/phf_ppc.hip, phf_ppc.h; DESIGN.md §3, "Posterior predictive checks").  Points, likelihoods and rows as

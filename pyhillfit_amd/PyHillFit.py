@@ -6,6 +6,7 @@
            [--diagnostics [--diagnostic-lags 256]] [--waic] [--loo [--loo-tail-per-chain 0]]
            [--quantiles [--quantile-probs 0.025,...,0.975] [--quantile-bins 16384] [--curve-bands G]] [--ppc]
            [--hierarchical --quantiles --predictive-bands G [--band-concs c1,c2,...]]
+           [--hierarchical --leave-experiment-out [--marginal-nodes 128] [--marginal-every T]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -20,7 +21,9 @@ credible intervals of every column over all chains (pyhillfit_amd/quantiles.py),
 dose-response curve at G doses, accumulated the same way; with --ppc, posterior predictive checks (test quantities of replicated
 data against the data, and the predictive PIT of every data point; pyhillfit_amd/ppc.py), accumulated the same way; with
 --hierarchical --quantiles --predictive-bands G, the quantiles of the dose-response curve of the inferred underlying effect and of a
-predicted future experiment at G doses (and at the named --band-concs), accumulated the same way.  The CMA-ES start point is replaced by a deterministic least-squares fit
+predicted future experiment at G doses (and at the named --band-concs), accumulated the same way; with --hierarchical
+--leave-experiment-out, the integrated leave-one-experiment-out cross-validation of every pair (pyhillfit_amd/marginal.py: each experiment's
+(Hill_i, pIC50_i) integrated out on the GPU, PSIS and WAIC over the experiments), written to the summary JSON as "loo_experiment".  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -83,6 +86,18 @@ def check_args(parser, args):
                 parser.error(str(e))
         if not args.predictive_bands:
             parser.error("--band-concs needs --predictive-bands")
+    if args.leave_experiment_out and not args.hierarchical:
+        parser.error("--leave-experiment-out needs --hierarchical (there are no experiment-level parameters to integrate out otherwise)")
+    if (args.marginal_nodes is not None or args.marginal_every is not None) and not args.leave_experiment_out:
+        parser.error("--marginal-nodes and --marginal-every need --leave-experiment-out")
+    if args.leave_experiment_out:
+        from .marginal import DEFAULT_EVERY, DEFAULT_NODES, NODE_CHOICES
+        args.marginal_nodes = DEFAULT_NODES if args.marginal_nodes is None else args.marginal_nodes
+        args.marginal_every = DEFAULT_EVERY if args.marginal_every is None else args.marginal_every
+        if args.marginal_nodes not in NODE_CHOICES:
+            parser.error("--marginal-nodes must be one of %s" % ", ".join(str(q) for q in NODE_CHOICES))
+        if args.marginal_every < 1:
+            parser.error("--marginal-every must be >= 1")
 
 
 def build_parser():
@@ -139,6 +154,14 @@ def build_parser():
                      "pair's smallest dose / 10 to its largest x 10; written to the summary JSON as \"hierarchical_bands\"")
     new.add_argument("--band-concs", type=str, default=None, metavar="c1,c2,...", help="--predictive-bands: named concentrations (uM, "
                      "all > 0, at most 64) appended after the grid (the reference's -c/--concs)")
+    new.add_argument("--leave-experiment-out", action='store_true', default=False, help="--hierarchical: integrated leave-one-experiment-out "
+                     "cross-validation: every experiment's (Hill_i, pIC50_i) integrated out against the population distribution of each "
+                     "draw on the GPU, then PSIS and WAIC over the experiments; written to the summary JSON as \"loo_experiment\"")
+    new.add_argument("--marginal-nodes", type=int, default=None, metavar="Q", help="--leave-experiment-out: nodes a side of the Q x Q rule, "
+                     "32, 64, 128 (default) or 256; raise it when the report names experiments with a quadrature gap above 0.01")
+    new.add_argument("--marginal-every", type=int, default=None, metavar="T", help="--leave-experiment-out: every T-th post-burn-in row "
+                     "of every chain is used (default 178: on the whole Crumb set at the default chains and Q = 128 the flag then adds no more than "
+                     "the sampling time; the cost is proportional to Q^2 / T)")
     new.add_argument("--ppc", action='store_true', default=False, help="posterior predictive checks: mid-p values of the deviance, mean, sd "
                      "and counts of 0 and 100 of data replicated from every post-burn-in draw of every chain against the data's, and the "
                      "predictive PIT of every data point, accumulated on the GPU while the rows stream past; written to the summary JSON as \"ppc\"")

@@ -19,6 +19,8 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_psis_workspace_bytes", "phf_psis_init", "phf_psis_accumulate", "phf_psis_reduce", "phf_quantiles_workspace_bytes",
            "phf_quantiles_init", "phf_quantiles_accumulate", "phf_quantiles_accumulate_curves", "phf_quantiles_reduce",
            "phf_quantiles_accumulate_hier_curves", "phf_hier_band_draws",
+           "phf_hier_marginal_loglik", "phf_hier_marginal_rows_used", "phf_hier_marginal_rows", "phf_waic_accumulate_given",
+           "phf_psis_accumulate_given",
            "phf_ppc_workspace_bytes", "phf_ppc_init", "phf_ppc_accumulate", "phf_ppc_reduce", "phf_ppc_replicate", "phf_stepping_stone_workspace_bytes",
            "phf_stepping_stone_init", "phf_stepping_stone_accumulate", "phf_stepping_stone_reduce", "phf_stepping_stone_reduce_joint",
            "phf_replica_exchange_stats_bytes", "phf_replica_exchange_stats_init", "phf_replica_exchange_stats_read",
@@ -105,6 +107,8 @@ def load():
     lib.phf_waic_workspace_bytes.restype = C.c_size_t
     lib.phf_waic_init.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp]
     lib.phf_waic_accumulate.argtypes = [pwp, i32, i32, vp, i64, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
+    lib.phf_waic_accumulate_given.argtypes = [pwp, vp, i64, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
+    lib.phf_psis_accumulate_given.argtypes = [pwp, vp, i64, i32, i32, i32, i64, i64, i32, vp, C.c_size_t, vp]
     lib.phf_waic_reduce.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
     lib.phf_psis_tail_length.argtypes = [i32, i64]
     lib.phf_psis_tail_length.restype = i64
@@ -122,6 +126,10 @@ def load():
     lib.phf_quantiles_accumulate_hier_curves.argtypes = [vp, i64, i32, i32, i32, vp, i32, i32, i32, i64, i64, vp, C.c_uint32, C.c_uint64,
                                                          vp, C.c_size_t, vp]
     lib.phf_hier_band_draws.argtypes = [i64, vp, vp, C.c_uint64, vp, vp]
+    lib.phf_hier_marginal_loglik.argtypes = [pwp, i32, vp, i32, i64, vp, vp, vp, vp]
+    lib.phf_hier_marginal_rows_used.argtypes = [i64, i64, i32]
+    lib.phf_hier_marginal_rows_used.restype = i64
+    lib.phf_hier_marginal_rows.argtypes = [pwp, i32, vp, i32, vp, i64, i32, i32, i32, i64, i32, vp, vp, vp, vp]
     lib.phf_quantiles_reduce.argtypes = [i32, i32, i32, i32, vp, i32, vp, C.c_size_t, vp, vp]
     lib.phf_ppc_workspace_bytes.argtypes = [i32, i32, i32, i64]
     lib.phf_ppc_workspace_bytes.restype = C.c_size_t

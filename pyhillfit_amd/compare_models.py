@@ -1,7 +1,7 @@
 """Compare fits by WAIC or PSIS-LOO: the elpd difference of every two summaries and its pointwise standard error (Vehtari, Gelman &
 Gabry 2017).
 
-    python -m pyhillfit_amd.compare_models SUMMARY_A SUMMARY_B [...] [--intersection] [--criterion {waic,loo}]
+    python -m pyhillfit_amd.compare_models SUMMARY_A SUMMARY_B [...] [--intersection] [--criterion {waic,loo,logo}]
 
 Each argument is a `<chain>_summary.json` written with --waic (--criterion waic, the default) or --loo (--criterion loo), or an
 output directory searched for them.  The summaries of each
@@ -16,7 +16,11 @@ y == 0 or 100) and the other a DENSITY (uncensored or the hierarchical truncated
 "mixed": their log-likelihoods are not on one scale.  Model 1 against model 2 has none; single-level against hierarchical has one per
 censored point.  With --criterion loo the pointwise elpd_loo are compared; a pair where either fit has a common point with Pareto
 k-hat above its threshold is marked ("khat_flagged": its difference rests on unreliable points), and a pair where either fit has a
-point without an elpd_loo (not determined, or -inf) is refused.  One JSON object on stdout, then a table on stderr."""
+point without an elpd_loo (not determined, or -inf) is refused.  With --criterion logo two HIERARCHICAL summaries written with
+--leave-experiment-out are compared (for example -Ne subsets or different seeds): the integrated leave-one-experiment-out elpd_i of the
+experiments both hold, aligned by the experiment's label; a single-level summary is refused (it has no experiment-level parameters to
+integrate out, and a pooled fit scored on the same scale would still give censored points a mass, not a density).  One JSON object
+on stdout, then a table on stderr."""
 import argparse
 import glob
 import json
@@ -26,6 +30,8 @@ import sys
 import numpy as np
 
 CENSORED = ("censored-0", "censored-100")
+OBJECT = {"waic": "waic", "loo": "loo", "logo": "loo_experiment"}       # the summary's object of each criterion
+FLAG = {"waic": "--waic", "loo": "--loo", "logo": "--hierarchical --leave-experiment-out"}
 
 
 def load_sources(path, criterion="waic"):
@@ -35,11 +41,14 @@ def load_sources(path, criterion="waic"):
     for f in files:
         with open(f) as fh:
             s = json.load(fh)
-        if criterion not in s:
+        if criterion == "logo" and "model" in s and "num_expts" not in s:
+            raise SystemExit("%s is a single-level summary (model %s): --criterion logo compares hierarchical fits only — the integrated "
+                             "leave-one-experiment-out integrates experiment-level parameters a single-level fit does not have" % (f, s["model"]))
+        if OBJECT[criterion] not in s:
             continue
         out[(s["drug"], s["channel"])] = dict(s, _file=f)
     if not out:
-        raise SystemExit("%s: no summary with a \"%s\" object (run with --%s)" % (path, criterion, criterion))
+        raise SystemExit("%s: no summary with a \"%s\" object (run with %s)" % (path, OBJECT[criterion], FLAG[criterion]))
     return out
 
 
@@ -96,6 +105,39 @@ def compare(wa, wb, intersection=False, criterion="waic"):
     return rec
 
 
+def compare_logo(wa, wb, intersection=False):
+    """two "loo_experiment" objects -> dict of the comparison over the experiments both hold (aligned by label)"""
+    ia = {e["label"]: e for e in wa["experiments"]}
+    ib = {e["label"]: e for e in wb["experiments"]}
+    common = [k for k in ia if k in ib]
+    only_a, only_b = len(ia) - len(common), len(ib) - len(common)
+    rec = {"n_points": len(common), "n_only_a": only_a, "n_only_b": only_b, "n_mixed": 0}
+    if (only_a or only_b) and not intersection:
+        rec["error"] = "experiment sets differ ({} only in A, {} only in B): use --intersection to compare the common experiments".format(only_a, only_b)
+        return rec
+    if any(ia[k]["n_i"] != ib[k]["n_i"] for k in common):
+        rec["error"] = "experiments with the same label hold different numbers of points: not the same data"
+        return rec
+    missing = [sum(1 for k in common if w[k]["elpd_i"] is None) for w in (ia, ib)]
+    if any(missing) or not common:
+        rec["error"] = "experiments without an elpd_i (not determined, or -inf): {} in A, {} in B".format(*missing) if common else "no common experiment"
+        return rec
+    ea = np.array([ia[k]["elpd_i"] for k in common], dtype=np.float64)
+    eb = np.array([ib[k]["elpd_i"] for k in common], dtype=np.float64)
+    d = ea - eb
+    n = len(d)
+    diff = float(np.sum(d))
+    se = float(np.sqrt(n * np.var(d, ddof=1))) if n > 1 else float("nan")
+    pref = "A" if diff > 2 * se else "B" if diff < -2 * se else "neither"
+    na = sum(1 for k in common if ia[k]["khat_i"] is None or ia[k]["khat_i"] > wa["khat_threshold"])
+    nb = sum(1 for k in common if ib[k]["khat_i"] is None or ib[k]["khat_i"] > wb["khat_threshold"])
+    ga = sum(1 for k in common if ia[k]["quadrature_gap_max"] is None or ia[k]["quadrature_gap_max"] > 0.01)
+    gb = sum(1 for k in common if ib[k]["quadrature_gap_max"] is None or ib[k]["quadrature_gap_max"] > 0.01)
+    rec.update({"elpd_a": float(np.sum(ea)), "elpd_b": float(np.sum(eb)), "elpd_diff": diff, "se_diff": se, "preferred": pref,
+                "n_khat_a": na, "n_khat_b": nb, "khat_flagged": bool(na or nb), "n_gap_a": ga, "n_gap_b": gb, "gap_flagged": bool(ga or gb)})
+    return rec
+
+
 def _num(v):
     return None if v is None or not np.isfinite(v) else v
 
@@ -106,7 +148,8 @@ def compare_sources(sources, names, intersection=False, criterion="waic"):
         for j in range(i + 1, len(sources)):
             for key in [k for k in sources[i] if k in sources[j]]:
                 sa, sb = sources[i][key], sources[j][key]
-                rec = compare(sa[criterion], sb[criterion], intersection, criterion)
+                rec = (compare_logo(sa[OBJECT["logo"]], sb[OBJECT["logo"]], intersection) if criterion == "logo" else
+                       compare(sa[criterion], sb[criterion], intersection, criterion))
                 rec = {k: (_num(v) if isinstance(v, float) else v) for k, v in rec.items()}
                 out.append(dict({"drug": key[0], "channel": key[1], "a": names[i], "b": names[j], "file_a": sa["_file"],
                                  "file_b": sb["_file"]}, **rec))
@@ -114,7 +157,7 @@ def compare_sources(sources, names, intersection=False, criterion="waic"):
 
 
 def table(rows, criterion="waic"):
-    if criterion == "loo":
+    if criterion in ("loo", "logo"):
         return _loo_table(rows)
     lines = ["{:<28} {:>10} {:>8} {:>8} {:>6} {:>7}".format("pair (A vs B)", "elpd_diff", "se", "pref.", "n", "mixed")]
     for r in rows:
@@ -144,8 +187,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="compare_models")
     ap.add_argument("summaries", nargs="+", help="<chain>_summary.json files written with --waic / --loo, or output directories")
     ap.add_argument("--intersection", action="store_true", help="compare the points two fits share when their point sets differ")
-    ap.add_argument("--criterion", choices=["waic", "loo"], default="waic",
-                    help="compare the pointwise elpd of WAIC (default) or of PSIS-LOO (summaries written with --loo)")
+    ap.add_argument("--criterion", choices=["waic", "loo", "logo"], default="waic",
+                    help="compare the pointwise elpd of WAIC (default), of PSIS-LOO (summaries written with --loo), or the per-experiment "
+                         "elpd of the integrated leave-one-experiment-out (hierarchical summaries written with --leave-experiment-out)")
     a = ap.parse_args(argv)
     if len(a.summaries) < 2:
         raise SystemExit("compare_models needs at least two summaries or directories")

@@ -29,6 +29,7 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kPtBlock = 4;             // points per wavefront of the accumulate kernel
 constexpr int kFields = 5;              // m, s, x0, A, B
 constexpr int kHierarchical = 3;        // `likelihood` of the hierarchical layout (1 | 2: single-level model 1 | 2)
+constexpr int kGiven = 4;               // phf_waic_accumulate_given: l of point p is column p of the row
 
 __device__ inline int clamp_tag(int t, int hi) { return t < 0 ? 0 : (t > hi ? hi : t); }
 __device__ inline int clamp_count(int n, int stride) { return n < 0 ? 0 : (n > stride ? stride : n); }
@@ -112,7 +113,7 @@ __device__ inline void waic_update(double l, bool first, double& m, double& s, d
 template <int LIK>
 __global__ __launch_bounds__(kThreads) void waic_accumulate_kernel(const WaicArgs a) {
   PHF_MATH_TABLES_TO_LDS();
-  if (LIK == kHierarchical) PHF_ERFC_TABLE_TO_LDS(); else PHF_LOGPHI_TABLE_TO_LDS();
+  if (LIK == kGiven) { } else if (LIK == kHierarchical) PHF_ERFC_TABLE_TO_LDS(); else PHF_LOGPHI_TABLE_TO_LDS();
   const int unit = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / 64));   // wave-uniform
   if (unit >= a.units) return;
   const int pb = unit % a.npb;
@@ -135,9 +136,9 @@ __global__ __launch_bounds__(kThreads) void waic_accumulate_kernel(const WaicArg
   for (int k = 0; k < kPtBlock; ++k) {
     const int p = k < np ? p0 + k : p0;                            // a block's missing points repeat its first (never stored)
     const size_t at = (size_t)q * ps + p;
-    lc[k] = a.pts.ln_conc[at];
-    yv[k] = a.pts.response[at];
-    tg[k] = clamp_tag(a.pts.tag[at], LIK == kHierarchical ? a.ne - 1 : 2);
+    lc[k] = LIK == kGiven ? 0.0 : a.pts.ln_conc[at];
+    yv[k] = LIK == kGiven ? 0.0 : a.pts.response[at];
+    tg[k] = LIK == kGiven ? 0 : clamp_tag(a.pts.tag[at], LIK == kHierarchical ? a.ne - 1 : 2);
 #pragma unroll
     for (int f = 0; f < kFields; ++f) acc[k][f] = k < np ? st[((size_t)k * kFields + f) * C] : 0.0;
   }
@@ -146,7 +147,11 @@ __global__ __launch_bounds__(kThreads) void waic_accumulate_kernel(const WaicArg
   for (int64_t r = 0; r < a.nr; ++r) {
     const double* x = xr + (size_t)r * rstep;
     const bool first = a.first_row + r == 0;
-    if (LIK == kHierarchical) {
+    if (LIK == kGiven) {
+#pragma unroll
+      for (int k = 0; k < kPtBlock; ++k)
+        if (k < np) waic_update(x[(size_t)(p0 + k) * C], first, acc[k][0], acc[k][1], acc[k][2], acc[k][3], acc[k][4], k_exp);
+    } else if (LIK == kHierarchical) {
       const phf_pw_sigma sg = phf_pw_sigma_terms(x[(size_t)(4 + 2 * a.ne) * C], k_log);
 #pragma unroll
       for (int k = 0; k < kPtBlock; ++k) {
@@ -315,25 +320,39 @@ extern "C" int phf_waic_init(int num_problems, int stride, int num_chains, int64
   return PHF_OK;
 }
 
-extern "C" int phf_waic_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
-                                   int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows,
-                                   double* workspace, size_t workspace_bytes, void* stream) {
-  static const char* who = "phf_waic_accumulate";
+namespace {
+
+// phf_waic_accumulate and phf_waic_accumulate_given (likelihood == kGiven): one validation, one launch
+int waic_accumulate(const char* who, const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
+                    int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, double* workspace,
+                    size_t workspace_bytes, void* stream) {
+  char msg[kPhfErrorBufferSize];
   int rc = check_points(who, pts, num_problems);
   if (rc != PHF_OK) return rc;
   if ((rc = check_shape(who, num_problems, pts->stride, num_chains, total_rows)) != PHF_OK) return rc;
-  if (likelihood < 1 || likelihood > kHierarchical)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: likelihood must be 1, 2 (single-level model) or 3 (hierarchical)");
-  if (likelihood == kHierarchical && num_expts < 1)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: the hierarchical likelihood needs num_expts >= 1");
-  const int cols = likelihood == kHierarchical ? 5 + 2 * num_expts : likelihood + 1;
-  if (row_stride_cols < cols)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: row_stride_cols is smaller than the columns the likelihood reads");
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
-  if (!rows || !workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, pts->stride, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: workspace smaller than phf_waic_workspace_bytes()");
+  if (likelihood != kGiven) {                                      // phf_waic_accumulate's own codes
+    if (likelihood < 1 || likelihood > kHierarchical)
+      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: likelihood must be 1, 2 (single-level model) or 3 (hierarchical)");
+    if (likelihood == kHierarchical && num_expts < 1)
+      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: the hierarchical likelihood needs num_expts >= 1");
+  }
+  const int cols = likelihood == kGiven ? pts->stride : likelihood == kHierarchical ? 5 + 2 * num_expts : likelihood + 1;
+  if (row_stride_cols < cols) {
+    std::snprintf(msg, sizeof msg, "%s: row_stride_cols is smaller than the columns the likelihood reads", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows) {
+    std::snprintf(msg, sizeof msg, "%s: rows [first_row, first_row + num_rows) must lie in [0, total_rows)", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (!rows || !workspace) {
+    std::snprintf(msg, sizeof msg, "%s: null pointer", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (workspace_bytes < workspace_bytes_of(num_problems, pts->stride, num_chains)) {
+    std::snprintf(msg, sizeof msg, "%s: workspace smaller than phf_waic_workspace_bytes()", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
   if (num_rows == 0) return PHF_OK;
   WaicArgs a = {};
   a.pts = *pts; a.rows = rows; a.nr = num_rows; a.first_row = first_row; a.total_rows = total_rows;
@@ -344,8 +363,26 @@ extern "C" int phf_waic_accumulate(const phf_pointwise_points* pts, int likeliho
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (likelihood == 1) hipLaunchKernelGGL(waic_accumulate_kernel<1>, grid, block, 0, s, a);
   else if (likelihood == 2) hipLaunchKernelGGL(waic_accumulate_kernel<2>, grid, block, 0, s, a);
-  else hipLaunchKernelGGL(waic_accumulate_kernel<kHierarchical>, grid, block, 0, s, a);
+  else if (likelihood == kHierarchical) hipLaunchKernelGGL(waic_accumulate_kernel<kHierarchical>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(waic_accumulate_kernel<kGiven>, grid, block, 0, s, a);
   return phf_check_launch("waic_accumulate_kernel");
+}
+
+}  // namespace
+
+extern "C" int phf_waic_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
+                                   int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows,
+                                   double* workspace, size_t workspace_bytes, void* stream) {
+  // the sibling's code is not this entry's to take: 0 fails the range check inside, after the points and the shape as before
+  return waic_accumulate("phf_waic_accumulate", pts, likelihood == kGiven ? 0 : likelihood, num_expts, rows, num_rows, num_problems, row_stride_cols, num_chains, first_row, total_rows,
+                         workspace, workspace_bytes, stream);
+}
+
+extern "C" int phf_waic_accumulate_given(const phf_pointwise_points* pts, const double* rows, int64_t num_rows, int num_problems,
+                                         int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, double* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  return waic_accumulate("phf_waic_accumulate_given", pts, kGiven, 0, rows, num_rows, num_problems, row_stride_cols, num_chains, first_row,
+                         total_rows, workspace, workspace_bytes, stream);
 }
 
 extern "C" int phf_waic_reduce(int num_problems, int stride, int num_chains, int64_t total_rows, const double* workspace,

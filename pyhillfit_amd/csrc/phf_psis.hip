@@ -53,6 +53,7 @@ constexpr int kPtBlock = 4;             // points per wavefront of the accumulat
 constexpr int kFields = 6;              // m_nt, s_nt, m_all, s_all, fill, inserts
 constexpr int kOut = 5;                 // elpd_loo, lppd, k-hat, sigma-hat, determined
 constexpr int kHierarchical = 3;        // `likelihood` of the hierarchical layout (1 | 2: single-level model 1 | 2)
+constexpr int kGiven = 4;               // phf_psis_accumulate_given: l of point p is column p of the row
 constexpr int kLdsTail = 8192;          // tail entries (M + 1) the reduce keeps in LDS; beyond, the HBM scratch
 constexpr int64_t kMaxTail = (1 << 20) - 1;   // the longest tail M accepted
 constexpr int kMaxGrid = 30 + 1024;     // Zhang-Stephens grid points: 30 + floor(sqrt(M)) <= 30 + 1023
@@ -160,7 +161,7 @@ __device__ inline void psis_take(double l, double T, double& h, int& f, double& 
 template <int LIK>
 __global__ __launch_bounds__(kThreads) void psis_accumulate_kernel(const PsisArgs a) {
   PHF_MATH_TABLES_TO_LDS();
-  if (LIK == kHierarchical) PHF_ERFC_TABLE_TO_LDS(); else PHF_LOGPHI_TABLE_TO_LDS();
+  if (LIK == kGiven) { } else if (LIK == kHierarchical) PHF_ERFC_TABLE_TO_LDS(); else PHF_LOGPHI_TABLE_TO_LDS();
   const int unit = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / 64));   // wave-uniform
   if (unit >= a.units) return;
   const int pb = unit % a.npb;
@@ -186,9 +187,9 @@ __global__ __launch_bounds__(kThreads) void psis_accumulate_kernel(const PsisArg
   for (int j = 0; j < kPtBlock; ++j) {
     const int p = j < np ? p0 + j : p0;                            // a block's missing points repeat its first (never stored)
     const size_t at = (size_t)q * ps + p;
-    lc[j] = a.pts.ln_conc[at];
-    yv[j] = a.pts.response[at];
-    tg[j] = clamp_tag(a.pts.tag[at], LIK == kHierarchical ? a.ne - 1 : 2);
+    lc[j] = LIK == kGiven ? 0.0 : a.pts.ln_conc[at];
+    yv[j] = LIK == kGiven ? 0.0 : a.pts.response[at];
+    tg[j] = LIK == kGiven ? 0 : clamp_tag(a.pts.tag[at], LIK == kHierarchical ? a.ne - 1 : 2);
     const double* sj = st + (size_t)j * kFields * C;
     const bool load = !fresh && j < np;
     thr[j] = load ? a.thr[at] : PHF_INF;
@@ -204,7 +205,16 @@ __global__ __launch_bounds__(kThreads) void psis_accumulate_kernel(const PsisArg
   const double* xr = a.rows + (size_t)q * a.stride_cols * C + c;
   for (int64_t r = 0; r < a.nr; ++r) {
     const double* x = xr + (size_t)r * rstep;
-    if (LIK == kHierarchical) {
+    if (LIK == kGiven) {
+#pragma unroll
+      for (int j = 0; j < kPtBlock; ++j) {
+        if (j < np) {
+          const double l = x[(size_t)(p0 + j) * C];
+          lse_add(l, m_all[j], s_all[j], k_exp);
+          psis_take(l, thr[j], h[j], f[j], m_nt[j], s_nt[j], ins[j], hp + (size_t)j * K * C, C, K, k_exp);
+        }
+      }
+    } else if (LIK == kHierarchical) {
       const phf_pw_sigma sg = phf_pw_sigma_terms(x[(size_t)(4 + 2 * a.ne) * C], k_log);
 #pragma unroll
       for (int j = 0; j < kPtBlock; ++j) {
@@ -711,26 +721,40 @@ extern "C" int phf_psis_init(int num_problems, int stride, int num_chains, int64
   return phf_check_launch("psis_init_thr_kernel");
 }
 
-extern "C" int phf_psis_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
-                                   int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows,
-                                   int tail_per_chain, double* workspace, size_t workspace_bytes, void* stream) {
-  static const char* who = "phf_psis_accumulate";
+namespace {
+
+// phf_psis_accumulate and phf_psis_accumulate_given (likelihood == kGiven): one validation, one launch loop
+int psis_accumulate(const char* who, const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
+                    int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, int tail_per_chain,
+                    double* workspace, size_t workspace_bytes, void* stream) {
+  char msg[kPhfErrorBufferSize];
   int rc = check_points(who, pts, num_problems);
   if (rc != PHF_OK) return rc;
   Layout L;
   if ((rc = layout_of(who, num_problems, pts->stride, num_chains, total_rows, tail_per_chain, &L)) != PHF_OK) return rc;
-  if (likelihood < 1 || likelihood > kHierarchical)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: likelihood must be 1, 2 (single-level model) or 3 (hierarchical)");
-  if (likelihood == kHierarchical && num_expts < 1)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: the hierarchical likelihood needs num_expts >= 1");
-  const int cols = likelihood == kHierarchical ? 5 + 2 * num_expts : likelihood + 1;
-  if (row_stride_cols < cols)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: row_stride_cols is smaller than the columns the likelihood reads");
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
-  if (!rows || !workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: null pointer");
-  if (workspace_bytes < L.bytes())
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: workspace smaller than phf_psis_workspace_bytes()");
+  if (likelihood != kGiven) {                                      // phf_psis_accumulate's own codes
+    if (likelihood < 1 || likelihood > kHierarchical)
+      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: likelihood must be 1, 2 (single-level model) or 3 (hierarchical)");
+    if (likelihood == kHierarchical && num_expts < 1)
+      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: the hierarchical likelihood needs num_expts >= 1");
+  }
+  const int cols = likelihood == kGiven ? pts->stride : likelihood == kHierarchical ? 5 + 2 * num_expts : likelihood + 1;
+  if (row_stride_cols < cols) {
+    std::snprintf(msg, sizeof msg, "%s: row_stride_cols is smaller than the columns the likelihood reads", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows) {
+    std::snprintf(msg, sizeof msg, "%s: rows [first_row, first_row + num_rows) must lie in [0, total_rows)", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (!rows || !workspace) {
+    std::snprintf(msg, sizeof msg, "%s: null pointer", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (workspace_bytes < L.bytes()) {
+    std::snprintf(msg, sizeof msg, "%s: workspace smaller than phf_psis_workspace_bytes()", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
   if (num_rows == 0) return PHF_OK;
   PsisArgs a = {};
   a.pts = *pts; a.rows = rows; a.nr = num_rows; a.first_row = first_row; a.total_rows = total_rows;
@@ -748,7 +772,8 @@ extern "C" int phf_psis_accumulate(const phf_pointwise_points* pts, int likeliho
     a.rows = rows + (size_t)(r - first_row) * rstep; a.first_row = r; a.nr = b - r;
     if (likelihood == 1) hipLaunchKernelGGL(psis_accumulate_kernel<1>, grid, block, 0, s, a);
     else if (likelihood == 2) hipLaunchKernelGGL(psis_accumulate_kernel<2>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(psis_accumulate_kernel<kHierarchical>, grid, block, 0, s, a);
+    else if (likelihood == kHierarchical) hipLaunchKernelGGL(psis_accumulate_kernel<kHierarchical>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(psis_accumulate_kernel<kGiven>, grid, block, 0, s, a);
     if ((rc = phf_check_launch("psis_accumulate_kernel")) != PHF_OK) return rc;
     if (b == nb && b < total_rows) {
       hipLaunchKernelGGL(psis_threshold_kernel, tgrid, block, 0, s, a);
@@ -757,6 +782,23 @@ extern "C" int phf_psis_accumulate(const phf_pointwise_points* pts, int likeliho
     r = b;
   }
   return PHF_OK;
+}
+
+}  // namespace
+
+extern "C" int phf_psis_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
+                                   int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows,
+                                   int tail_per_chain, double* workspace, size_t workspace_bytes, void* stream) {
+  // the sibling's code is not this entry's to take: 0 fails the range check inside, after the points and the layout as before
+  return psis_accumulate("phf_psis_accumulate", pts, likelihood == kGiven ? 0 : likelihood, num_expts, rows, num_rows, num_problems,
+                         row_stride_cols, num_chains, first_row, total_rows, tail_per_chain, workspace, workspace_bytes, stream);
+}
+
+extern "C" int phf_psis_accumulate_given(const phf_pointwise_points* pts, const double* rows, int64_t num_rows, int num_problems,
+                                         int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, int tail_per_chain,
+                                         double* workspace, size_t workspace_bytes, void* stream) {
+  return psis_accumulate("phf_psis_accumulate_given", pts, kGiven, 0, rows, num_rows, num_problems, row_stride_cols, num_chains, first_row,
+                         total_rows, tail_per_chain, workspace, workspace_bytes, stream);
 }
 
 extern "C" int phf_psis_reduce(const phf_pointwise_points* pts, int num_problems, int num_chains, int64_t total_rows, int tail_per_chain,

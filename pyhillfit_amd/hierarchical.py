@@ -535,6 +535,16 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             psis = lo.PointwiseLOO(lpts, "hierarchical", Q, C, saved_iterations - burn, device, args.loo_tail_per_chain)
             if burn == 0:
                 psis.accumulate(s.row0.unsqueeze(0).contiguous())
+        logo = None
+        if getattr(args, "leave_experiment_out", False):               # integrated leave-one-experiment-out, accumulated like PSIS-LOO
+            from . import marginal as mg
+            from . import waic as wc
+            from .PyHillFit import experiments_and_labels
+            mpts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
+            mg.check_memory(mg.workspace_bytes(Q, ne, C, saved_iterations - burn, args.marginal_every, seg // thinning), device)
+            logo = mg.ExperimentLOO(mpts, Q, C, saved_iterations - burn, args.marginal_nodes, args.marginal_every, device)
+            if burn == 0:
+                logo.accumulate(s.row0.unsqueeze(0).contiguous())
         quant = None
         if getattr(args, "quantiles", False):                          # posterior quantiles over all chains, accumulated like the diagnostics
             from . import quantiles as qn
@@ -561,7 +571,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             if burn == 0:
                 ppc.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, waic=waic, psis=psis, quant=quant, ppc=ppc, stream=torch.cuda.Stream(device=device)))
+                         diag=diag, waic=waic, psis=psis, logo=logo, quant=quant, ppc=ppc, stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
     fused = None
@@ -616,6 +626,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     run["waic"].accumulate(rows[first:])
                 if run["psis"] is not None and first < nr:
                     run["psis"].accumulate(rows[first:])
+                if run["logo"] is not None and first < nr:
+                    run["logo"].accumulate(rows[first:])
                 if run["quant"] is not None and first < nr:
                     run["quant"].accumulate(rows[first:])
                 if run["ppc"] is not None and first < nr:
@@ -641,6 +653,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     loo_names, loo_parts = [], []
     quant_names, quant_parts = [], []
     ppc_names, ppc_parts = [], []
+    logo_names, logo_parts, logo_labels = [], [], []
     band_nf = 0
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
@@ -655,6 +668,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         loo_res = run["psis"].result() if run["psis"] is not None else None
         if loo_res is not None:
             run["psis"].free()
+        logo_res = run["logo"].result() if run["logo"] is not None else None
+        if logo_res is not None:
+            run["logo"].free()
         quant_res = run["quant"].result() if run["quant"] is not None else None
         if quant_res is not None:
             run["quant"].free()
@@ -689,6 +705,13 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                 summ["loo"] = lo.json_record(loo_res[q], run["psis"].points, q, run["psis"].M, run["psis"].k)
                 loo_names.append("{} + {}".format(d_clean, c_clean))
                 loo_parts.append(loo_res[q])
+            if logo_res is not None:
+                from . import marginal as mg
+                labels = [e[0] for e in run["logo"].epoints.info[q]]
+                summ["loo_experiment"] = mg.json_record(logo_res[q], labels, run["logo"].nodes, run["logo"].every)
+                logo_names.append("{} + {}".format(d_clean, c_clean))
+                logo_parts.append(logo_res[q])
+                logo_labels.append(labels)
             if quant_res is not None:
                 from . import quantiles as qn
                 summ["quantiles"] = qn.json_record(quant_res, q, hierarchical_columns(ne), args.quantile_bins)
@@ -717,6 +740,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     if getattr(args, "loo", False):
         from . import loo as lo
         print(lo.report_line(rank, loo_names, loo_parts))
+    if getattr(args, "leave_experiment_out", False):
+        from . import marginal as mg
+        print(mg.report_line(rank, logo_names, logo_parts, logo_labels))
     if getattr(args, "quantiles", False):
         from . import quantiles as qn
         print(qn.report_line(rank, quant_names, quant_parts, band_nf if getattr(args, "predictive_bands", 0) else None))

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from .sampler import _ptr, _stream_ptr
-from .waic import DevicePoints, _likelihood, _num, columns_read
+from .waic import GIVEN, DevicePoints, _likelihood, _num, columns_read
 
 HIERARCHICAL = 3
 METHOD = ("PSIS-LOO (Vehtari, Simpson, Gelman, Yao & Gabry 2024; r_eff = 1): log ratios r = -log p(y_i | theta_s) over all chains' "
@@ -96,7 +96,8 @@ def finalize(elpd_loo_i, lppd_i, khat_i, sigma_i, determined_i, S):
 class PointwiseLOO(object):
     """Streaming PSIS-LOO of num_problems problems over `chains` chains and total_rows post-burn-in rows.  accumulate() takes the rows
     in order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride >= columns][chains] (asynchronous, on the
-    current stream); result() reduces and finalizes.  kind: 1 | 2 (single-level model) or "hierarchical"; tail_per_chain: the heap
+    current stream); result() reduces and finalizes.  kind: 1 | 2 (single-level model), "hierarchical" or "given" (waic.Points.given:
+    column p of a row is the log-likelihood of point p); tail_per_chain: the heap
     capacity per (point, chain), 0 for the default rule."""
 
     def __init__(self, points, kind, num_problems, chains, total_rows, device="cuda", tail_per_chain=0):
@@ -131,9 +132,14 @@ class PointwiseLOO(object):
             raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
         if n == 0:
             return
-        _lib.check(self.lib.phf_psis_accumulate(C.byref(self.dp.struct), self.lik, self.ne, _ptr(rows), n, self.Q, rows.shape[2], self.C,
-                                                self.rows_seen, self.N, self.requested, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                                _stream_ptr(self.device)), "phf_psis_accumulate")
+        if self.lik == GIVEN:
+            _lib.check(self.lib.phf_psis_accumulate_given(C.byref(self.dp.struct), _ptr(rows), n, self.Q, rows.shape[2], self.C, self.rows_seen,
+                                                          self.N, self.requested, _ptr(self.ws), C.c_size_t(self.nbytes),
+                                                          _stream_ptr(self.device)), "phf_psis_accumulate_given")
+        else:
+            _lib.check(self.lib.phf_psis_accumulate(C.byref(self.dp.struct), self.lik, self.ne, _ptr(rows), n, self.Q, rows.shape[2], self.C,
+                                                    self.rows_seen, self.N, self.requested, _ptr(self.ws), C.c_size_t(self.nbytes),
+                                                    _stream_ptr(self.device)), "phf_psis_accumulate")
         self.rows_seen += n
 
     def reduced(self, tail=False):

@@ -24,6 +24,7 @@ from .sampler import _ptr, _stream_ptr
 
 P_WARN = 0.4
 HIERARCHICAL = 3                        # phf_waic_accumulate's `likelihood` for the hierarchical layout (1 | 2: single-level model)
+GIVEN = 4                               # phf_waic_accumulate_given: l of point p is column p of the row (kind "given")
 KINDS = ("uncensored", "censored-0", "censored-100")
 METHOD = ("WAIC (Watanabe 2010; Vehtari, Gelman & Gabry 2017): lppd_i = log mean_s p(y_i | theta_s), p_waic_i = var_s log p(y_i | theta_s) "
           "(divisor S - 1), elpd_i = lppd_i - p_waic_i, se = sqrt(n var(elpd_i)); per data point over all chains' post-burn-in draws")
@@ -68,6 +69,11 @@ class Points(object):
         return cls(out)
 
     @classmethod
+    def given(cls, labels_per_problem):
+        """"points" whose log-likelihood is handed in (kind "given"): one per label, e.g. the experiments of a hierarchical pair"""
+        return cls([[(lab, 1.0, 0.0, 0, "given") for lab in labels] for labels in labels_per_problem])
+
+    @classmethod
     def hierarchical(cls, experiments_per_problem, labels_per_problem=None):
         """every problem with the same number Ne of experiments (one launch group); every point, truncated-normal"""
         ne = {len(e) for e in experiments_per_problem}
@@ -102,12 +108,14 @@ def _likelihood(kind, points):
         if points.num_expts is None:
             raise ValueError("the hierarchical likelihood needs hierarchical points")
         return HIERARCHICAL, points.num_expts
+    if kind == "given":
+        return GIVEN, 0
     raise ValueError("kind must be 1, 2 (single-level model) or 'hierarchical', got %r" % (kind,))
 
 
 def columns_read(kind, points):
     lik, ne = _likelihood(kind, points)
-    return 5 + 2 * ne if lik == HIERARCHICAL else lik + 1
+    return points.stride if lik == GIVEN else 5 + 2 * ne if lik == HIERARCHICAL else lik + 1
 
 
 def pointwise_loglik(points, kind, problem_index, theta, device="cuda"):
@@ -156,7 +164,8 @@ def finalize(lppd_sum_lse, var, S):
 class PointwiseWAIC(object):
     """Streaming WAIC of num_problems problems over `chains` chains and total_rows post-burn-in rows.  accumulate() takes the rows in
     order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride >= columns][chains] (asynchronous, on the
-    current stream); result() reduces and finalizes.  kind: 1 | 2 (single-level model) or "hierarchical"."""
+    current stream); result() reduces and finalizes.  kind: 1 | 2 (single-level model), "hierarchical", or "given": column p of a
+    row IS the log-likelihood of point p (Points.given)."""
 
     def __init__(self, points, kind, num_problems, chains, total_rows, device="cuda"):
         self.lib = _lib.load()
@@ -187,9 +196,14 @@ class PointwiseWAIC(object):
             raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
         if n == 0:
             return
-        _lib.check(self.lib.phf_waic_accumulate(C.byref(self.dp.struct), self.lik, self.ne, _ptr(rows), n, self.Q, rows.shape[2], self.C,
-                                                self.rows_seen, self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
-                   "phf_waic_accumulate")
+        if self.lik == GIVEN:
+            _lib.check(self.lib.phf_waic_accumulate_given(C.byref(self.dp.struct), _ptr(rows), n, self.Q, rows.shape[2], self.C, self.rows_seen,
+                                                          self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
+                       "phf_waic_accumulate_given")
+        else:
+            _lib.check(self.lib.phf_waic_accumulate(C.byref(self.dp.struct), self.lik, self.ne, _ptr(rows), n, self.Q, rows.shape[2], self.C,
+                                                    self.rows_seen, self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
+                       "phf_waic_accumulate")
         self.rows_seen += n
 
     def reduced(self):
