@@ -75,6 +75,7 @@ struct AdvanceArgs {
   // work queue (phf_single_level_advance_queued): queue[0] = next task, queue[1 + b] = quanta of block b that are complete
   int32_t* queue;
   int32_t quantum;
+  int32_t steady;                              // 0: every call runs the general iteration (PHF_SL_STEADY=0, advance_impl)
 };
 
 // stage one pair's entries into LDS (lc = s_pts, y = s_pts + stride, w = s_pts + 2 stride); returns counts
@@ -99,7 +100,10 @@ __device__ __forceinline__ void stage_points(const phf_points& pts, int pair, do
 // ln_conc bits instead of evaluating it again (phf_sl_log_target_shared): each iteration the uncensored entries write their
 // denominators to this wavefront's LDS slots s_den[j][lane] (ds_write2st64_b64: one per two entries), and a shared entry reads slot
 // den_off[m] / kBlock — one ds_read_b64 in place of ~19 VALU, nearly all fp64.  Same doubles, same results.
-template <int MODEL, bool MOMENTS, int KO, int KC, unsigned SHARE, bool LONE_WAVE>
+// STEADY: the caller has checked t_begin >= adapt_start, so every iteration of this call adapts and none is the reset step (t ==
+// adapt_start): gamma[t - adapt_start] is used as read and the mean takes the covariance's weights — no compare, no select, and the
+// fp64 operations that remain are the general iteration's, in its order.
+template <int MODEL, bool MOMENTS, int KO, int KC, unsigned SHARE, bool LONE_WAVE, bool STEADY>
 __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double* s_pts, double* s_den, const int* den_off, int q,
                                              int c, int pair, int n_other_rt, int n_cens_rt, const int64_t t_begin, const int64_t t_end) {
   static_assert(SHARE == 0 || (KO >= 1 && KO <= kDenSlots && KC >= 1 && KC <= kMaxShared && (SHARE >> KC) == 0),
@@ -138,7 +142,9 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
 #pragma unroll
   for (int i = 0; i < NTRI; ++i) cov[i] = sp[(size_t)(2 * D + 1 + i) * nchains];
   double loga = sp[(size_t)(2 * D + 1 + NTRI) * nchains];
-  double nacc = sp[(size_t)(2 * D + 2 + NTRI) * nchains];
+  const double nacc_in = sp[(size_t)(2 * D + 2 + NTRI) * nchains];
+  uint32_t nacc = 0;      // accepts of THIS call, counted as an integer (a call has fewer than 2^32 iterations): nacc_in + nacc below is
+                          // the sum the iterations' + 1.0 would give, all of them integers far below 2^53
   double ll1 = sp[(size_t)(2 * D + 3 + NTRI) * nchains];   // untempered log-likelihood of the current state
   // exp and log coefficients: in VGPRs for the whole launch (8 doubles)
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
@@ -177,8 +183,19 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
   uint32_t w_u = 0u;
   if constexpr (D == 3) w_u = phf_mh_draws_w3(cid, pid, (uint32_t)(t_begin + 1), seed_lo, seed_hi, z);
   else log_u = phf_mh_draws(D, cid, pid, (uint32_t)(t_begin + 1), seed_lo, seed_hi, k_log, z);
-  const bool reset_mean = a.cfg.reset_mean_at_adapt_start != 0;
-  for (int64_t t = t_begin + 1; t <= t_end; ++t) {
+  // Iteration bookkeeping in 32 bits (advance_impl refuses t_end > 0xffffffff): gfx950 has no scalar 64-bit ordering compare, so a
+  // 64-bit t costs the vector pipe a copy and a v_cmp_*_i64 per test.  `left` counts down (t itself may end at 0xffffffff); the two
+  // 64-bit thresholds become a 32-bit value and flags for the cases it cannot express, fixed before the loop.
+  const int64_t adapt_start = a.cfg.adapt_start;
+  const bool adapt_in_range = adapt_start >= 0 && adapt_start <= 0xffffffffLL;
+  const bool adapt_always = adapt_start < 0;                                              // t > adapt_start for every t
+  const uint32_t adapt_at = adapt_start > 0xffffffffLL ? 0xffffffffu : (uint32_t)adapt_start;   // (used only when !adapt_always)
+  const bool reset_mean = a.cfg.reset_mean_at_adapt_start != 0 && adapt_in_range;
+  const bool moments_always = a.moments_after < 0;
+  const uint32_t moments_at = a.moments_after > 0xffffffffLL ? 0xffffffffu : (uint32_t)a.moments_after;
+  int64_t gamma_i = t_begin + 1 - adapt_start;                                            // t - adapt_start: scalar adds, off the vector pipe
+  uint32_t t = (uint32_t)t_begin + 1u;
+  for (uint32_t left = (uint32_t)(t_end - t_begin); left != 0; --left, ++t, ++gamma_i) {
     // ---- proposal: theta* = theta + e^(loga/2) L z  (PyHillFit.py:831) ----
     double star[D];
 #pragma unroll
@@ -200,14 +217,21 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
       lt = lt_star;
       ll1 = ll1_star;
     }
-    nacc += acc ? 1.0 : 0.0;
+    nacc += acc ? 1u : 0u;
     // ---- adaptation (PyHillFit.py:840-846; PyHillTemp.py:114-122), wave-uniform selects instead of branches ----
-    const bool adapting = t > a.cfg.adapt_start;
-    const bool reset_now = reset_mean && t == a.cfg.adapt_start;                       // PyHillTemp.py:114-115: mean <- theta
-    const double gs_tab = a.cfg.gamma[adapting ? t - a.cfg.adapt_start : 0];
-    const double gs = adapting ? gs_tab : 0.0;
-    const double omg = 1.0 - gs;
-    const double gm = reset_now ? 1.0 : gs, omm = reset_now ? 0.0 : omg;               // mean: 1 theta + 0 mean on the reset step
+    double gs, gm, omg, omm;
+    if constexpr (STEADY) {
+      gs = a.cfg.gamma[gamma_i];
+      omg = 1.0 - gs;
+      gm = gs; omm = omg;
+    } else {
+      const bool adapting = adapt_always || t > adapt_at;
+      const bool reset_now = reset_mean && t == adapt_at;                              // PyHillTemp.py:114-115: mean <- theta
+      const double gs_tab = a.cfg.gamma[adapting ? gamma_i : 0];
+      gs = adapting ? gs_tab : 0.0;
+      omg = 1.0 - gs;
+      gm = reset_now ? 1.0 : gs; omm = reset_now ? 0.0 : omg;                          // mean: 1 theta + 0 mean on the reset step
+    }
     {
       double v[D];
 #pragma unroll
@@ -225,8 +249,8 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
     double z_next[3];
     double log_u_next = 0.0;
     uint32_t w_u_next = 0u;
-    if constexpr (D == 3) w_u_next = phf_mh_draws_w3(cid, pid, (uint32_t)(t + 1), seed_lo, seed_hi, z_next);
-    else log_u_next = phf_mh_draws(D, cid, pid, (uint32_t)(t + 1), seed_lo, seed_hi, k_log, z_next);
+    if constexpr (D == 3) w_u_next = phf_mh_draws_w3(cid, pid, t + 1u, seed_lo, seed_hi, z_next);
+    else log_u_next = phf_mh_draws(D, cid, pid, t + 1u, seed_lo, seed_hi, k_log, z_next);
     chol_packed<D>(cov, L);
     sc = phf_exp_fast_k(0.5 * loga, k_exp);
 #pragma unroll
@@ -242,7 +266,7 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
         out[(size_t)D * C] = lt;
         out += row_stride;
       }
-      if (want_moments && t > a.moments_after) {
+      if (want_moments && (moments_always || t > moments_at)) {
 #pragma unroll
         for (int i = 0; i < D; ++i) { m1[i] += th[i]; m2[i] = phf_fma(th[i], th[i], m2[i]); }
         m1[D] += lt; m2[D] = phf_fma(lt, lt, m2[D]);
@@ -260,7 +284,7 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
 #pragma unroll
   for (int i = 0; i < NTRI; ++i) sp[(size_t)(2 * D + 1 + i) * nchains] = cov[i];
   sp[(size_t)(2 * D + 1 + NTRI) * nchains] = loga;
-  sp[(size_t)(2 * D + 2 + NTRI) * nchains] = nacc;
+  sp[(size_t)(2 * D + 2 + NTRI) * nchains] = nacc_in + (double)nacc;
   sp[(size_t)(2 * D + 3 + NTRI) * nchains] = ll1;
   if (want_moments) {
 #pragma unroll
@@ -280,11 +304,11 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
 // Hill denominators shared (SHARE, advance_body): the masks below are the ones the Crumb pairs have (two pairs or more; 141 of the
 // 210 pairs run one, sharing 290 of the 310 shareable censored entries).  A pair runs it when its censored entries include the
 // mask's (sharing fewer entries than it could is still the same arithmetic); every other pair runs the no-sharing body of its shape.
-#define PHF_BODY_(ko, kc, sh) \
-  advance_body<MODEL, MOMENTS, ko, kc, sh, WPS == 1>(a, s_pts, s_den, den_off, q, c, pair, n_other, n_cens, t_begin, t_end)
-#define PHF_SHAPE_CASE(ko, kc) case (ko) * 8 + (kc): PHF_BODY_(ko, kc, 0u); break;
+#define PHF_BODY_(ko, kc, sh, steady) \
+  advance_body<MODEL, MOMENTS, ko, kc, sh, WPS == 1, steady>(a, s_pts, s_den, den_off, q, c, pair, n_other, n_cens, t_from, t_to)
+#define PHF_SHAPE_CASE(ko, kc) case (ko) * 8 + (kc): PHF_BODY_(ko, kc, 0u, true); break;
 #define PHF_SHAPE_CASE_SHARED(ko, kc, sh) \
-  case (ko) * 8 + (kc): if ((share & (sh)) == (sh)) PHF_BODY_(ko, kc, sh); else PHF_BODY_(ko, kc, 0u); break;
+  case (ko) * 8 + (kc): if ((share & (sh)) == (sh)) PHF_BODY_(ko, kc, sh, true); else PHF_BODY_(ko, kc, 0u, true); break;
 #define PHF_SHAPE_ROW(ko) PHF_SHAPE_CASE(ko, 0) PHF_SHAPE_CASE(ko, 1) PHF_SHAPE_CASE(ko, 2) PHF_SHAPE_CASE(ko, 3) PHF_SHAPE_CASE(ko, 4)
 
 // Bit m set: censored entry m has the ln_conc bits of an uncensored entry j < kDenSlots, and den_off[m] = j * kBlock (the first
@@ -320,6 +344,17 @@ __device__ __forceinline__ void run_block(const AdvanceArgs& a, double* s_pts, d
   const int n_cens = n_zero + n_hundred;
   int den_off[kMaxShared];
   const unsigned share = share_map(s_pts, n_other, n_cens, den_off);
+  // The straight-line bodies exist as STEADY only (a second set would double the code object).  The iterations of this call up to
+  // adapt_start — none in all but the first 1 000 d iterations of a run — take the general iteration with the run-time loops, the same
+  // operations in the same order; the rest of the SAME call then continues in a steady body from the state and the row position the
+  // general part left in memory (each lane reads back what it wrote itself, exactly as the next launch would).  All wave-uniform.
+  int64_t t_from = t_begin, t_to = t_end;
+  if (a.steady == 0 || t_begin < a.cfg.adapt_start) {
+    if (a.steady != 0 && a.cfg.adapt_start < t_end) t_to = a.cfg.adapt_start;
+    PHF_BODY_(-1, -1, 0u, false);
+    if (t_to == t_end) return;
+    t_from = t_to; t_to = t_end;
+  }
   if (n_other <= 5 && n_cens <= 4) {
     switch (n_other * 8 + n_cens) {                     // wave-uniform
       PHF_SHAPE_CASE(0, 1) PHF_SHAPE_CASE(0, 2) PHF_SHAPE_CASE(0, 3) PHF_SHAPE_CASE(0, 4)
@@ -331,11 +366,11 @@ __device__ __forceinline__ void run_block(const AdvanceArgs& a, double* s_pts, d
       PHF_SHAPE_CASE(4, 0) PHF_SHAPE_CASE_SHARED(4, 1, 0x1u) PHF_SHAPE_CASE_SHARED(4, 2, 0x3u) PHF_SHAPE_CASE_SHARED(4, 3, 0x7u)
       PHF_SHAPE_CASE_SHARED(4, 4, 0xfu)
       PHF_SHAPE_ROW(5)
-      default: PHF_BODY_(-1, -1, 0u); break;
+      default: PHF_BODY_(-1, -1, 0u, true); break;
     }
     return;
   }
-  PHF_BODY_(-1, -1, 0u);
+  PHF_BODY_(-1, -1, 0u, true);
 }
 
 // WPS = wavefronts per SIMD the register allocation allows for: 2 (256 registers) for launches that fill the chip more than
@@ -597,7 +632,10 @@ static int advance_impl(const phf_points* pts, const phf_problems* prob, const p
   if (int rc = phf_require_device_memory(state, "state")) return rc;
   if (int rc = phf_require_device_memory(moments, "moments")) return rc;
   if (int rc = phf_require_device_memory(queue, "queue workspace")) return rc;
-  AdvanceArgs a{*pts, *prob, *cfg, t_begin, t_end, state, rows, moments, moments_after, 0, nullptr, 0};
+  // PHF_SL_STEADY=0 in the environment (read once): every call runs the general iteration, whatever its t_begin — for same-build A/B
+  // runs and the bit-identity test of the steady bodies
+  static const bool steady_on = [] { const char* e = getenv("PHF_SL_STEADY"); return !(e && e[0] == '0' && e[1] == 0); }();
+  AdvanceArgs a{*pts, *prob, *cfg, t_begin, t_end, state, rows, moments, moments_after, 0, nullptr, 0, steady_on ? 1 : 0};
   a.blocks_per_problem = (prob->chains_per_problem + kBlock - 1) / kBlock;
   const int64_t nblocks = (int64_t)a.blocks_per_problem * prob->num_problems;
   const size_t lds = (size_t)pts->stride * 24;
