@@ -673,6 +673,50 @@ int phf_replica_exchange_labels_init(int num_pairs, int rungs_per_pair, int num_
 int phf_replica_exchange_round(const phf_problems* prob, int model, int rungs_per_pair, int64_t round, uint64_t seed, double* state,
                                int32_t* labels, int64_t* stats, size_t stats_bytes, double* trace, void* stream);
 
+/* ---- power-scaling sensitivity of prior and likelihood ----------------------------------------------------------------------
+ * (pyhillfit_amd/csrc/phf_sensitivity.hip, phf_sensitivity.h; DESIGN.md §3, "Power-scaling sensitivity"; Kallioinen, Paananen,
+ * Buerkner & Vehtari 2023).  Scaling a component c(theta) of the log-target by alpha re-weights every draw by exp((alpha - 1) c); the
+ * components are the log-prior and the log-likelihood, the directions alpha = 1/(1 + delta) and 1 + delta, 0 < delta <= 0.25.
+ *   kind 1 | 2   single-level model 1 | 2, theta = columns 0..model of a row, sl_points = the sampler's merged entries (pair q <->
+ *                problem q): prior = phf_sl_log_prior, likelihood = the untempered log-likelihood, their sum the log-target at t = 1;
+ *   kind 3       hierarchical, hier_points (n_expts = Ne, pair q <-> problem q) and prior: prior = the five Gamma hyper-priors,
+ *                likelihood = the truncated-normal data term; the population terms belong to neither;
+ *   kind 4       given: columns prior_column and likelihood_column of the row are the two components (points and prior unused).
+ * Per (problem, component) c_ref = the first finite component in (row, chain) order of all rows accumulated; a draw's weight is
+ * w = exp(clamp((alpha - 1)(c - c_ref), -8, 8)), its integer mass floor(w 2^20 + 1/2).  A draw whose component is not finite enters
+ * nothing of that component.  Per (problem, column) slot, columns 0..num_columns-1 of the rows, on one grid by the quantiles' rule
+ * (anchor, w0, least level holding [min, max]): the base counts and the four mass arrays (prior down, prior up, likelihood down,
+ * likelihood up), uint64 — identical however the rows arrive or are cut into calls.  Per (problem, weight, chain), in row order:
+ * n, sum w, sum w^2, clamped draws; per (slot, array, chain): sum w, sum w d, sum w d^2, d = x - the slot's anchor (array 0: w = 1).
+ *   rows        device [num_rows][num_problems][row_stride_cols][num_chains]; calls in row order, [first_row, first_row + num_rows)
+ *               within total_rows; total_rows x num_chains <= 2^32
+ *   bins        a power of two in [64, 4096]
+ *   workspace   device, phf_sensitivity_workspace_bytes(...): the slots' arrays, the sums, and a scratch region of about 256 MiB (at
+ *               least 16 rows, at most total_rows) through which an accumulate call walks its rows in blocks; phf_sensitivity_init zeroes it (stream-ordered)
+ *   out_slots   device [S][28], S = num_problems x num_columns: min, max, binned draws, non-finite values, bin width, level, anchor,
+ *               w0; then per weight the sums of the cumulative Jensen-Shannon divergence over the bins from the first to the last one
+ *               holding a draw — numerator and denominator on the CDF, numerator and denominator on the survival function — and the
+ *               total mass (phf_sens_cjs_sums)
+ *   out_weights device [num_problems][4][4]: per weight n, sum w, sum w^2, clamped draws, the chains merged in chain order
+ *   out_columns device [S][5][4]: per array sum w, sum w d, sum w d^2 merged in chain order, and the between-chain standard error of
+ *               the weighted mean's shift from the base mean (in units of x; NaN for array 0 or fewer than two chains)
+ *   out_per_chain  NULL, or device [num_problems][4][4][num_chains] then [S][5][3][num_chains] doubles: the per-chain sums (tests)
+ * Every argument is checked before any launch: PHF_ERR_INVALID_ARGUMENT / 0 bytes without touching a GPU (phf_last_error() says why). */
+size_t phf_sensitivity_workspace_bytes(int num_problems, int num_columns, int num_chains, int64_t total_rows, int bins);
+int phf_sensitivity_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, int bins, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int phf_sensitivity_accumulate(int kind, const phf_points* sl_points, const phf_hier_points* hier_points, const phf_hier_prior* prior,
+                               int prior_column, int likelihood_column, const double* rows, int64_t num_rows, int num_problems,
+                               int row_stride_cols, int num_chains, int num_columns, double delta, int bins, int64_t first_row,
+                               int64_t total_rows, void* workspace, size_t workspace_bytes, void* stream);
+int phf_sensitivity_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, int bins, const void* workspace,
+                           size_t workspace_bytes, double* out_slots, double* out_weights, double* out_columns, double* out_per_chain,
+                           void* stream);
+/* Batch evaluator: theta [d][m] (d = kind + 1, or 5 + 2 Ne), problem_index [m]; out [3][m] = prior, likelihood, and the population
+ * term (0 for the single-level models); NaN for a problem index out of range.  Serves the tests and the chain-file tool. */
+int phf_sensitivity_components(int kind, const phf_points* sl_points, const phf_hier_points* hier_points, const phf_hier_prior* prior,
+                               int64_t m, const int32_t* problem_index, const double* theta, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
            [--quantiles [--quantile-probs 0.025,...,0.975] [--quantile-bins 16384] [--curve-bands G]] [--ppc]
            [--hierarchical --quantiles --predictive-bands G [--band-concs c1,c2,...]]
            [--hierarchical --leave-experiment-out [--marginal-nodes 128] [--marginal-every T]]
+           [--sensitivity [--sensitivity-delta 0.01] [--sensitivity-bins 4096] [--sensitivity-threshold 0.05]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -23,7 +24,9 @@ data against the data, and the predictive PIT of every data point; pyhillfit_amd
 --hierarchical --quantiles --predictive-bands G, the quantiles of the dose-response curve of the inferred underlying effect and of a
 predicted future experiment at G doses (and at the named --band-concs), accumulated the same way; with --hierarchical
 --leave-experiment-out, the integrated leave-one-experiment-out cross-validation of every pair (pyhillfit_amd/marginal.py: each experiment's
-(Hill_i, pIC50_i) integrated out on the GPU, PSIS and WAIC over the experiments), written to the summary JSON as "loo_experiment".  The CMA-ES start point is replaced by a deterministic least-squares fit
+(Hill_i, pIC50_i) integrated out on the GPU, PSIS and WAIC over the experiments), written to the summary JSON as "loo_experiment"; with
+--sensitivity, the power-scaling sensitivity of every parameter column to the prior and to the likelihood (pyhillfit_amd/sensitivity.py),
+accumulated the same way and written to the summary JSON as "sensitivity".  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -86,6 +89,18 @@ def check_args(parser, args):
                 parser.error(str(e))
         if not args.predictive_bands:
             parser.error("--band-concs needs --predictive-bands")
+    sens_given = [n for n in ("sensitivity_delta", "sensitivity_bins", "sensitivity_threshold") if getattr(args, n, None) is not None]
+    if sens_given and not getattr(args, "sensitivity", False):
+        parser.error("--%s needs --sensitivity" % sens_given[0].replace("_", "-"))
+    if getattr(args, "sensitivity", False):
+        from . import sensitivity as sn
+        try:
+            args.sensitivity_delta = sn.check_delta(sn.DEFAULT_DELTA if args.sensitivity_delta is None else args.sensitivity_delta)
+            args.sensitivity_bins = sn.check_bins(sn.DEFAULT_BINS if args.sensitivity_bins is None else args.sensitivity_bins)
+            args.sensitivity_threshold = sn.check_threshold(sn.DEFAULT_THRESHOLD if args.sensitivity_threshold is None
+                                                            else args.sensitivity_threshold)
+        except ValueError as e:
+            parser.error(str(e))
     if args.leave_experiment_out and not args.hierarchical:
         parser.error("--leave-experiment-out needs --hierarchical (there are no experiment-level parameters to integrate out otherwise)")
     if (args.marginal_nodes is not None or args.marginal_every is not None) and not args.leave_experiment_out:
@@ -165,6 +180,15 @@ def build_parser():
     new.add_argument("--ppc", action='store_true', default=False, help="posterior predictive checks: mid-p values of the deviance, mean, sd "
                      "and counts of 0 and 100 of data replicated from every post-burn-in draw of every chain against the data's, and the "
                      "predictive PIT of every data point, accumulated on the GPU while the rows stream past; written to the summary JSON as \"ppc\"")
+    new.add_argument("--sensitivity", action='store_true', default=False, help="power-scaling sensitivity (Kallioinen et al. 2023): how far every "
+                     "parameter's posterior moves when the prior, or the likelihood, is raised to a power a little off 1, from re-weighted "
+                     "histograms accumulated on the GPU while the rows stream past; written to the summary JSON as \"sensitivity\"")
+    new.add_argument("--sensitivity-delta", type=float, default=None, metavar="DELTA", help="--sensitivity: the powers are 1/(1 + DELTA) and "
+                     "1 + DELTA; 0 < DELTA <= 0.25 (default 0.01)")
+    new.add_argument("--sensitivity-bins", type=int, default=None, metavar="B", help="--sensitivity: histogram bins per column, a power of two "
+                     "in [64, 4096] (default 4096)")
+    new.add_argument("--sensitivity-threshold", type=float, default=None, metavar="TAU", help="--sensitivity: a column is flagged when its "
+                     "sensitivity D exceeds TAU (default 0.05)")
     new.add_argument("--fused-launch", choices=["auto", "on", "off"], default="auto",
                      help="--hierarchical: the launch groups the gfx950 code object has kernels for (Ne = 3; Ne = 4 with 4 + 4 + 4 + 1 / 2 / 3 points) through "
                           "ONE persistent grid per segment instead of a launch each (auto: when the run's chains give every SIMD a wavefront); same numbers")
@@ -288,6 +312,14 @@ def run_single_level(pairs, args, device, rank=0, world=1):
                                           [p[4] for p in pairs_with_ids(pairs, loaded)], 0, device)
         if burn == 0:
             ppc.accumulate(s.row0.unsqueeze(0).contiguous())
+    sens = None
+    if getattr(args, "sensitivity", False):
+        from . import sensitivity as sn
+        sn.check_memory(sn.workspace_bytes(Q, d, C, saved_iterations - burn, args.sensitivity_bins), device)
+        sens = sn.PowerScaling(s.points, model, Q, C, d, saved_iterations - burn, args.sensitivity_delta, args.sensitivity_bins, device,
+                               threshold=args.sensitivity_threshold)
+        if burn == 0:
+            sens.accumulate(s.row0.unsqueeze(0).contiguous())
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
             chainio.host_buffer((saved_iterations, Q, d + 1, 1)))   # pinned: chain 0 leaves the GPU asynchronously
     kept[0] = s.row0 if keep_all else s.row0[:, :, :1].cpu()
@@ -311,6 +343,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             quant.accumulate(rows[first:])
         if ppc is not None and first < nr:
             ppc.accumulate(rows[first:])
+        if sens is not None and first < nr:
+            sens.accumulate(rows[first:])
         # stream-ordered and asynchronous: the next segment is queued behind this copy while the host moves on (a blocking copy
         # here left the GPU idle for the gather + transfer + launch latency of every segment)
         kept[r:r + nr].copy_(rows if keep_all else rows[:, :, :, :1], non_blocking=True)
@@ -331,6 +365,9 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     ppc_res = ppc.result() if ppc is not None else None
     if ppc is not None:
         ppc.free()
+    sens_res = sens.result() if sens is not None else None
+    if sens is not None:
+        sens.free()
     summaries = []
     for q, (d_clean, c_clean, chain_file) in enumerate(files):
         chain0 = kept[:, q, :, 0].cpu().numpy()
@@ -357,6 +394,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
                 summ["curve_band"] = qn.curve_band_record(quant_res, q, doses[q])
         if ppc_res is not None:
             summ["ppc"] = pp.json_record(ppc_res[q], ppts, q)
+        if sens_res is not None:
+            summ["sensitivity"] = sn.json_record(sens_res, q, dr.file_labels)
         with open(chain_file[:-4] + "_summary.json", "w") as f:
             json.dump(summ, f, indent=1)
         summaries.append(summ)
@@ -375,6 +414,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
                               for q in range(len(files))]))
     if ppc_res is not None:
         print(pp.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], ppc_res))
+    if sens_res is not None:
+        print(sn.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], [sn.part_of(sens_res, q) for q in range(len(files))]))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, Q * C, total_iterations, time.time() - start - elapsed))
     return summaries

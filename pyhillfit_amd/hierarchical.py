@@ -570,8 +570,17 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                                               device)
             if burn == 0:
                 ppc.accumulate(s.row0.unsqueeze(0).contiguous())
+        sens = None
+        if getattr(args, "sensitivity", False):                        # power-scaling sensitivity, accumulated like the quantiles
+            from . import sensitivity as sn
+            sn.check_memory(sn.workspace_bytes(Q, d, C, saved_iterations - burn, args.sensitivity_bins), device)
+            sens = sn.PowerScaling(s.points, "hierarchical", Q, C, d, saved_iterations - burn, args.sensitivity_delta,
+                                   args.sensitivity_bins, device, prior=prior, threshold=args.sensitivity_threshold)
+            if burn == 0:
+                sens.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, waic=waic, psis=psis, logo=logo, quant=quant, ppc=ppc, stream=torch.cuda.Stream(device=device)))
+                         diag=diag, waic=waic, psis=psis, logo=logo, quant=quant, ppc=ppc, sens=sens,
+                         stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
     fused = None
@@ -632,6 +641,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     run["quant"].accumulate(rows[first:])
                 if run["ppc"] is not None and first < nr:
                     run["ppc"].accumulate(rows[first:])
+                if run["sens"] is not None and first < nr:
+                    run["sens"].accumulate(rows[first:])
                 run["kept"][run["r"]:run["r"] + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # chain 0 of each pair
                 ev = torch.cuda.Event()
                 ev.record(run["stream"])
@@ -653,6 +664,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     loo_names, loo_parts = [], []
     quant_names, quant_parts = [], []
     ppc_names, ppc_parts = [], []
+    sens_names, sens_parts = [], []
     logo_names, logo_parts, logo_labels = [], [], []
     band_nf = 0
     for run in runs:
@@ -677,6 +689,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         ppc_res = run["ppc"].result() if run["ppc"] is not None else None
         if ppc_res is not None:
             run["ppc"].free()
+        sens_res = run["sens"].result() if run["sens"] is not None else None
+        if sens_res is not None:
+            run["sens"].free()
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
@@ -727,6 +742,11 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                 summ["ppc"] = pp.json_record(ppc_res[q], run["ppc"].points, q)
                 ppc_names.append("{} + {}".format(d_clean, c_clean))
                 ppc_parts.append(ppc_res[q])
+            if sens_res is not None:
+                from . import sensitivity as sn
+                summ["sensitivity"] = sn.json_record(sens_res, q, hierarchical_columns(ne)[:5 + 2 * ne])
+                sens_names.append("{} + {}".format(d_clean, c_clean))
+                sens_parts.append(sn.part_of(sens_res, q))
             with open(chain_file[:-4] + "_summary.json", "w") as f:
                 json.dump(summ, f, indent=1)
             summaries.append(summ)
@@ -749,6 +769,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     if getattr(args, "ppc", False):
         from . import ppc as pp
         print(pp.report_line(rank, ppc_names, ppc_parts))
+    if getattr(args, "sensitivity", False):
+        from . import sensitivity as sn
+        print(sn.report_line(rank, sens_names, sens_parts))
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, total_chains, total_iterations, time.time() - start - elapsed))
     return summaries
