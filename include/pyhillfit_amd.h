@@ -673,6 +673,34 @@ int phf_replica_exchange_labels_init(int num_pairs, int rungs_per_pair, int num_
 int phf_replica_exchange_round(const phf_problems* prob, int model, int rungs_per_pair, int64_t round, uint64_t seed, double* state,
                                int32_t* labels, int64_t* stats, size_t stats_bytes, double* trace, void* stream);
 
+/* ---- differential-evolution moves between the chains of a pair of the hierarchical sampler ----------------------------------
+ * (pyhillfit_amd/csrc/phf_hier_de.hip, phf_hier_de.h; DESIGN.md §3, "Differential-evolution moves"; ter Braak 2006).  pts, prob, prior
+ * and state are the hierarchical sampler's.  The chains of a problem form populations of `population` = 4, 8, 16, 32 or 64 consecutive
+ * chains by global chain number (chain_id_base + chain_offset[q] + c; chains_per_problem, chain_id_base and every chain_offset must be
+ * multiples of it).  Round `round` (1 <= round < 2^32) is two launches in stream order, sub-round h = 0 then 1: the chains whose index
+ * within the population has parity h move, the n = population / 2 chains of the other parity are donors and are only read.  With
+ * w0..w3 the Philox block counter = (global chain id, problem id, round, 0x20000000 | h), key = seed:
+ *   a' = floor(w0 n / 2^32), b' = floor(w1 (n-1) / 2^32), b' += (b' >= a'); donors a = min, b = max; sign from the top bit of w2;
+ *   x' = x + (sign gamma)(x_a - x_b), one subtraction, multiplication and addition per coordinate;
+ *   accept iff log u < L(x') - L(x), u = (w3 + 1/2) / 2^32, L(x) the state's log-target, L(x') the sampler's own target function.
+ * A NaN or L(x') = -inf rejects.  On accept theta and the log-target of the state change: mean, factor, loga and the sampler's accepted
+ * count do not.  The proposal is symmetric, so a round leaves the product of the chains' posteriors invariant; chains of one
+ * population are no longer independent of each other afterwards, populations stay independent.
+ *   gamma      > 0; gamma == 1.0 exactly marks a mode-jumping round (counted apart)
+ *   workspace  device, phf_hier_de_workspace_bytes(n_expts, Q, C) = (5 + 2 n_expts) Q C doubles: the proposals (scratch between launches)
+ *   stats      device, phf_hier_de_stats_bytes(Q, C): int64 attempts and accepts per (kind of round, problem, 64-chain block), kind 0 =
+ *              ordinary, 1 = gamma == 1; one writer per counter, no atomics; phf_hier_de_stats_init zeroes it
+ *   trace      device double [Q][C][6] or NULL: donor chains a and b (numbers within the problem), sign gamma, log u, L(x'), accepted
+ * phf_hier_de_stats_read writes int64 [2 kinds][attempts, accepts][Q] to out (device), the chain blocks summed in order.
+ * Every argument is checked before any launch: PHF_ERR_INVALID_ARGUMENT / 0 bytes without touching a GPU (phf_last_error() says why). */
+size_t phf_hier_de_workspace_bytes(int n_expts, int num_problems, int num_chains);
+size_t phf_hier_de_stats_bytes(int num_problems, int num_chains);
+int phf_hier_de_stats_init(int num_problems, int num_chains, int64_t* stats, size_t stats_bytes, void* stream);
+int phf_hier_de_stats_read(int num_problems, int num_chains, const int64_t* stats, size_t stats_bytes, int64_t* out, void* stream);
+int phf_hier_de_round(const phf_hier_points* pts, const phf_problems* prob, const phf_hier_prior* prior, int64_t round, uint64_t seed,
+                      int population, double gamma, double* state, double* workspace, size_t workspace_bytes, int64_t* stats,
+                      size_t stats_bytes, double* trace, void* stream);
+
 /* ---- power-scaling sensitivity of prior and likelihood ----------------------------------------------------------------------
  * (pyhillfit_amd/csrc/phf_sensitivity.hip, phf_sensitivity.h; DESIGN.md §3, "Power-scaling sensitivity"; Kallioinen, Paananen,
  * Buerkner & Vehtari 2023).  Scaling a component c(theta) of the log-target by alpha re-weights every draw by exp((alpha - 1) c); the

@@ -8,6 +8,7 @@
            [--hierarchical --quantiles --predictive-bands G [--band-concs c1,c2,...]]
            [--hierarchical --leave-experiment-out [--marginal-nodes 128] [--marginal-every T]]
            [--sensitivity [--sensitivity-delta 0.01] [--sensitivity-bins 4096] [--sensitivity-threshold 0.05]]
+           [--hierarchical --de-every K [--de-population 64] [--de-gamma GAMMA] [--de-jump-every 10]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -113,6 +114,22 @@ def check_args(parser, args):
             parser.error("--marginal-nodes must be one of %s" % ", ".join(str(q) for q in NODE_CHOICES))
         if args.marginal_every < 1:
             parser.error("--marginal-every must be >= 1")
+    de_given = [n for n in ("de_population", "de_gamma", "de_jump_every") if getattr(args, n, None) is not None]
+    if args.de_every < 0:
+        parser.error("--de-every must be >= 0 (0 = no differential-evolution moves)")
+    if args.de_every and not args.hierarchical:
+        parser.error("--de-every needs --hierarchical (the moves are between the chains of the hierarchical sampler; PyHillTemp has --swap-every)")
+    if de_given and not args.de_every:
+        parser.error("--%s needs --de-every" % de_given[0].replace("_", "-"))
+    if args.de_every:
+        from . import de_moves as de
+        args.de_population = de.DEFAULT_POPULATION if args.de_population is None else args.de_population
+        args.de_jump_every = de.DEFAULT_JUMP_EVERY if args.de_jump_every is None else args.de_jump_every
+        chains = DEFAULT_CHAINS_HIERARCHICAL if args.num_chains is None else args.num_chains
+        try:
+            de.check_settings(args.de_every, args.thinning, args.de_population, chains, args.de_gamma, args.de_jump_every)
+        except ValueError as e:
+            parser.error("--de-every / --de-population / --de-gamma / --de-jump-every: " + str(e))
 
 
 def build_parser():
@@ -189,6 +206,15 @@ def build_parser():
                      "in [64, 4096] (default 4096)")
     new.add_argument("--sensitivity-threshold", type=float, default=None, metavar="TAU", help="--sensitivity: a column is flagged when its "
                      "sensitivity D exceeds TAU (default 0.05)")
+    new.add_argument("--de-every", type=int, default=0, metavar="K", help="--hierarchical: differential-evolution moves between the chains of "
+                     "each pair (ter Braak 2006) after every K iterations, K a multiple of the thinning (default 0 = off: every output as "
+                     "without the flag); the chains of one population are then coupled; written to the summary JSON as \"de_moves\"")
+    new.add_argument("--de-population", type=int, default=None, metavar="G", help="--de-every: chains per population, 4, 8, 16, 32 or 64 "
+                     "(default 64); must divide --num-chains")
+    new.add_argument("--de-gamma", type=float, default=None, metavar="GAMMA", help="--de-every: the step factor (default 2.38 / sqrt(2 dim), "
+                     "dim = 5 + 2 experiments)")
+    new.add_argument("--de-jump-every", type=int, default=None, metavar="J", help="--de-every: every J-th round uses gamma = 1, a jump "
+                     "between modes (default 10; 0 = never)")
     new.add_argument("--fused-launch", choices=["auto", "on", "off"], default="auto",
                      help="--hierarchical: the launch groups the gfx950 code object has kernels for (Ne = 3; Ne = 4 with 4 + 4 + 4 + 1 / 2 / 3 points) through "
                           "ONE persistent grid per segment instead of a launch each (auto: when the run's chains give every SIMD a wavefront); same numbers")

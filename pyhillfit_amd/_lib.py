@@ -24,7 +24,8 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_ppc_workspace_bytes", "phf_ppc_init", "phf_ppc_accumulate", "phf_ppc_reduce", "phf_ppc_replicate", "phf_stepping_stone_workspace_bytes",
            "phf_stepping_stone_init", "phf_stepping_stone_accumulate", "phf_stepping_stone_reduce", "phf_stepping_stone_reduce_joint",
            "phf_replica_exchange_stats_bytes", "phf_replica_exchange_stats_init", "phf_replica_exchange_stats_read",
-           "phf_replica_exchange_labels_init", "phf_replica_exchange_round", "phf_sensitivity_workspace_bytes", "phf_sensitivity_init",
+           "phf_replica_exchange_labels_init", "phf_replica_exchange_round", "phf_hier_de_workspace_bytes", "phf_hier_de_stats_bytes",
+           "phf_hier_de_stats_init", "phf_hier_de_stats_read", "phf_hier_de_round", "phf_sensitivity_workspace_bytes", "phf_sensitivity_init",
            "phf_sensitivity_accumulate", "phf_sensitivity_reduce", "phf_sensitivity_components"]
 
 
@@ -150,6 +151,13 @@ def load():
     lib.phf_replica_exchange_stats_read.argtypes = [i32, i32, i32, vp, C.c_size_t, vp, vp]
     lib.phf_replica_exchange_labels_init.argtypes = [i32, i32, i32, vp, vp]
     lib.phf_replica_exchange_round.argtypes = [C.POINTER(Problems), i32, i32, i64, C.c_uint64, vp, vp, vp, C.c_size_t, vp, vp]
+    lib.phf_hier_de_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.phf_hier_de_workspace_bytes.restype = C.c_size_t
+    lib.phf_hier_de_stats_bytes.argtypes = [i32, i32]
+    lib.phf_hier_de_stats_bytes.restype = C.c_size_t
+    lib.phf_hier_de_stats_init.argtypes = [i32, i32, vp, C.c_size_t, vp]
+    lib.phf_hier_de_stats_read.argtypes = [i32, i32, vp, C.c_size_t, vp, vp]
+    lib.phf_hier_de_round.argtypes = [vp, C.POINTER(Problems), vp, i64, C.c_uint64, i32, f64, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
     lib.phf_sensitivity_workspace_bytes.argtypes = [i32, i32, i32, i64, i32]
     lib.phf_sensitivity_workspace_bytes.restype = C.c_size_t
     lib.phf_sensitivity_init.argtypes = [i32, i32, i32, i64, i32, vp, C.c_size_t, vp]

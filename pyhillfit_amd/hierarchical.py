@@ -242,6 +242,7 @@ class HierarchicalSampler(object):
         self._queue = None
         self.prob.kernel_hint |= 64
         self.quantum = 0
+        self.de = None                       # differential-evolution moves between advances (enable_de_moves): off
 
     @property
     def queue(self):
@@ -292,7 +293,42 @@ class HierarchicalSampler(object):
     def rows_between(self, t_begin, t_end):
         return t_end // self.thinning - t_begin // self.thinning
 
+    def enable_de_moves(self, every, population=None, gamma=None, jump_every=None):
+        """Differential-evolution moves between the chains of each pair (pyhillfit_amd/de_moves.py): after every `every` iterations —
+        a multiple of the thinning — round t / every updates each chain once from two other chains of its population of `population`
+        consecutive chains (default 64); gamma defaults to 2.38 / sqrt(2 dim), every jump_every-th round (default 10; 0 = never) uses 1.
+        every = 0 switches them off (the default: every output is then what it is without this call)."""
+        from . import de_moves as de
+        if not every:
+            self.de = None
+            return None
+        self.de = de.DEMoves(self, every, de.DEFAULT_POPULATION if population is None else population, gamma,
+                             de.DEFAULT_JUMP_EVERY if jump_every is None else jump_every)
+        return self.de
+
     def advance(self, n_iterations, out=None, save=True):
+        if self.de is None:
+            return self._advance_once(n_iterations, out=out, save=save)
+        # sub-advances that end at the multiples of K, round t / K after the one that reaches t, on the stream the advance used
+        from .de_moves import cut_points
+        t_end = self.t + int(n_iterations)
+        rows = None
+        if save:
+            shape = (self.rows_between(self.t, t_end), self.Q, self.d + 1, self.C)
+            rows = torch.empty(shape, dtype=torch.float64, device=self.device) if out is None else out
+            if tuple(rows.shape) != shape or not rows.is_contiguous():
+                raise ValueError("out must be contiguous with shape %s" % (shape,))
+        self.reserve(t_end)
+        r = 0
+        for nxt in cut_points(self.t, t_end, self.de.every):
+            nr = self.rows_between(self.t, nxt)
+            self._advance_once(nxt - self.t, out=rows[r:r + nr] if save else None, save=save)
+            r += nr
+            if nxt % self.de.every == 0:
+                self.de.round(nxt // self.de.every)
+        return rows
+
+    def _advance_once(self, n_iterations, out=None, save=True):
         t_end = self.t + int(n_iterations)
         cfg = self._config(t_end)
         rows = None
@@ -391,6 +427,41 @@ class FusedSamplers(object):
 
     def advance(self, n_iterations, out=None, save=True):
         """out: one tensor per sampler (as HierarchicalSampler.advance's), or None"""
+        moves = [s.de for s in self.samplers]
+        if all(m is None for m in moves):
+            return self._advance_once(n_iterations, out=out, save=save)
+        # differential-evolution moves (HierarchicalSampler.enable_de_moves): one fused launch per stretch between two multiples of K,
+        # then every group's round on this stream
+        if any(m is None for m in moves) or len({m.every for m in moves}) != 1:
+            raise ValueError("fused launch: differential-evolution moves in every sampler, with one interval, or in none")
+        from .de_moves import cut_points
+        K = moves[0].every
+        t0 = self.samplers[0].t
+        if any(s.t != t0 for s in self.samplers):
+            raise ValueError("fused launch: the samplers stand at different iterations")
+        t_end = t0 + int(n_iterations)
+        rows = [None] * len(self.samplers)
+        if save:
+            for j, s in enumerate(self.samplers):
+                shape = (s.rows_between(t0, t_end), s.Q, s.d + 1, s.C)
+                rows[j] = torch.empty(shape, dtype=torch.float64, device=self.device) if out is None else out[j]
+                if tuple(rows[j].shape) != shape or not rows[j].is_contiguous():
+                    raise ValueError("out[%d] must be contiguous with shape %s" % (j, shape))
+        for s in self.samplers:
+            s.reserve(t_end)
+        r = [0] * len(self.samplers)
+        t = t0
+        for nxt in cut_points(t0, t_end, K):
+            nrs = [s.rows_between(t, nxt) for s in self.samplers]
+            self._advance_once(nxt - t, out=[x[a:a + n] for x, a, n in zip(rows, r, nrs)] if save else None, save=save)
+            r = [a + n for a, n in zip(r, nrs)]
+            t = nxt
+            if t % K == 0:
+                for m in moves:
+                    m.round(t // K)
+        return rows
+
+    def _advance_once(self, n_iterations, out=None, save=True):
         t0 = self.samplers[0].t
         if any(s.t != t0 for s in self.samplers):
             raise ValueError("fused launch: the samplers stand at different iterations")
@@ -412,7 +483,7 @@ class FusedSamplers(object):
         if rc == _lib.PHF_ERR_UNSUPPORTED:
             # what the one grid does not take (a launch that starts between two saved rows, PHF_HIER_ISA=0 ...): the samplers' own launches,
             # one after the other on this stream — the same numbers
-            return [s.advance(n_iterations, out=r, save=save) for s, r in zip(self.samplers, rows)]
+            return [s._advance_once(n_iterations, out=r, save=save) for s, r in zip(self.samplers, rows)]
         _lib.check(rc, "phf_hierarchical_advance_fused")
         for s in self.samplers:
             s.t = t_end
@@ -495,6 +566,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         s.init(theta0, cov_scale=0.01)                                 # :431
         s.enable_moments(after_iteration=max(burn * thinning - 1, 0))
         s.reserve(total_iterations)
+        if getattr(args, "de_every", 0):                               # differential-evolution moves between the chains of each pair
+            s.enable_de_moves(args.de_every, args.de_population, args.de_gamma, args.de_jump_every)
         kept = chainio.host_buffer((saved_iterations, Q, d + 1))   # pinned: the per-segment copies are asynchronous
         kept[0] = s.row0[:, :, 0].cpu()
         files = []
@@ -666,6 +739,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     ppc_names, ppc_parts = [], []
     sens_names, sens_parts = [], []
     logo_names, logo_parts, logo_labels = [], [], []
+    de_names, de_parts = [], []
     band_nf = 0
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
@@ -692,6 +766,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         sens_res = run["sens"].result() if run["sens"] is not None else None
         if sens_res is not None:
             run["sens"].free()
+        de_res = s.de.records() if s.de is not None else None
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
@@ -710,6 +785,14 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                                                      columns=hierarchical_columns(ne))
                 diag_names.append("{} + {}".format(d_clean, c_clean))
                 diag_parts.append((diag_res["rhat"][q], diag_res["ess"][q]))
+                if de_res is not None:
+                    from . import de_moves as de
+                    summ["diagnostics"]["chains_coupled_within_populations_of"] = s.de.G
+                    summ["diagnostics"]["note"] = de.COUPLING_NOTE.format(G=s.de.G)
+            if de_res is not None:
+                summ["de_moves"] = de_res[q]
+                de_names.append("{} + {}".format(d_clean, c_clean))
+                de_parts.append(de_res[q])
             if waic_res is not None:
                 from . import waic as wc
                 summ["waic"] = wc.json_record(waic_res[q], run["waic"].points, q)
@@ -754,6 +837,12 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     chain_streams.close()
     if getattr(args, "diagnostics", False):
         print(dg.report_line(rank, diag_names, [p_[0] for p_ in diag_parts], [p_[1] for p_ in diag_parts]))
+        if getattr(args, "de_every", 0):
+            from . import de_moves as de
+            print("diagnostics [rank {}]: {}".format(rank, de.COUPLING_NOTE.format(G=args.de_population)))
+    if getattr(args, "de_every", 0):
+        from . import de_moves as de
+        print(de.report_line(rank, de_names, de_parts))
     if getattr(args, "waic", False):
         from . import waic as wc
         print(wc.report_line(rank, waic_names, waic_parts))
