@@ -393,6 +393,33 @@ int phf_diagnostics_accumulate(const double* rows, int64_t num_rows, int num_pro
 int phf_diagnostics_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags, const double* workspace,
                            size_t workspace_bytes, double* out, void* stream);
 
+/* ---- ESS and MCSE beyond the lag limit: batch means on a dyadic ladder of batch sizes -----------------------------------------
+ * The "blocking" method (Flyvbjerg & Petersen 1989; the estimator behind mcmcse) for chains whose autocorrelation time exceeds what
+ * phf_diagnostics_* can sum.  Half-chains as above (h = floor(total_rows / 2) >= 2, M = 2C).  Per (problem, column, chain, half), with
+ * y = x - (the half's first value): levels l = 0..NL-1, NL = floor(log2 h) + 1, batches of b = 2^l rows aligned to the half's start
+ * (trailing rows that fill no batch are not used at that level); a batch sum of level l+1 is (left child) + (right child); per level
+ * S1 = sum of the batch sums and S2 = sum of their squares, in batch order (pyhillfit_amd/csrc/phf_batch_means.h).  Deterministic: no
+ * atomics, bit-identical however the rows are cut into accumulate calls.  rows, first_row, total_rows, stream: as for
+ * phf_diagnostics_accumulate; the same error codes.
+ *   workspace  device, phf_batch_means_workspace_bytes(...) = num_problems * num_columns * num_chains * (5 NL + 2) doubles, laid out
+ *              [problem][column][field][chain] with the fields x0[2] | pending[NL] | S1[half 0][NL] | S2[half 0][NL] | S1[half 1][NL] |
+ *              S2[half 1][NL]; phf_batch_means_init zeroes it (stream-ordered)
+ *   out        device [num_problems][num_columns][NL + 1]: for l = 0..NL-2 (the levels with n_l = floor(h / b) >= 2 batches) the mean
+ *              over the 2C half-chains of the variance of the batch means, (S2 - S1^2 / n_l) / ((n_l - 1) b^2) (l = 0: W); then the mean of
+ *              the half-chain means; then their variance with divisor 2C - 1 (= B/h).  Sums over chains: lane l of a wavefront takes
+ *              chains l, l + 64, ... (half 0's term + half 1's), then a butterfly over lane distances 32, 16, .., 1.
+ * phf_batch_means_workspace_bytes returns 0 for an invalid shape (phf_last_error() says why); phf_batch_means_levels returns NL or a
+ * negative code. */
+size_t phf_batch_means_workspace_bytes(int num_problems, int num_columns, int num_chains, int64_t total_rows);
+int phf_batch_means_levels(int64_t total_rows);
+int phf_batch_means_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, double* workspace, size_t workspace_bytes,
+                         void* stream);
+int phf_batch_means_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                               int num_columns, int64_t first_row, int64_t total_rows, double* workspace, size_t workspace_bytes,
+                               void* stream);
+int phf_batch_means_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, const double* workspace,
+                           size_t workspace_bytes, double* out, void* stream);
+
 /* ---- pointwise log-likelihood and WAIC -------------------------------------------------------------------------------------
  * The terms are per DATA POINT (not per merged entry).  Points of problem q are row q of the arrays, in any order the caller keeps
  * (pyhillfit_amd/waic.py: data-file order); point p < count[q] of problem q has log-likelihood, for one parameter vector:

@@ -3,7 +3,7 @@
     python -m pyhillfit_amd.PyHillFit --data-file ../data/crumb_data.csv -m 2 -a [--hierarchical]
            [-i 500000] [-t 5] [-b 4] [-c N] [-Ne 0] [--num-APs 500] [-bfo]
            [--num-chains 64 | 128 with --hierarchical] [--seed 25] [--device cuda:0] [--save-all-chains] [--segment 20000]
-           [--diagnostics [--diagnostic-lags 256]] [--waic] [--loo [--loo-tail-per-chain 0]]
+           [--diagnostics [--diagnostic-lags 256] [--diagnostic-batch-means]] [--waic] [--loo [--loo-tail-per-chain 0]]
            [--quantiles [--quantile-probs 0.025,...,0.975] [--quantile-bins 16384] [--curve-bands G]] [--ppc]
            [--hierarchical --quantiles --predictive-bands G [--band-concs c1,c2,...]]
            [--hierarchical --leave-experiment-out [--marginal-nodes 128] [--marginal-every T]]
@@ -90,6 +90,8 @@ def check_args(parser, args):
                 parser.error(str(e))
         if not args.predictive_bands:
             parser.error("--band-concs needs --predictive-bands")
+    if getattr(args, "diagnostic_batch_means", False) and not args.diagnostics:
+        parser.error("--diagnostic-batch-means needs --diagnostics")
     sens_given = [n for n in ("sensitivity_delta", "sensitivity_bins", "sensitivity_threshold") if getattr(args, n, None) is not None]
     if sens_given and not getattr(args, "sensitivity", False):
         parser.error("--%s needs --sensitivity" % sens_given[0].replace("_", "-"))
@@ -163,6 +165,9 @@ def build_parser():
     new.add_argument("--diagnostics", action='store_true', default=False, help="split-R-hat, multi-chain ESS and MCSE of every column over all chains, "
                      "accumulated on the GPU while the rows stream past; written to the summary JSON as \"diagnostics\"")
     new.add_argument("--diagnostic-lags", type=int, default=256, help="lag limit K of the autocorrelation sums of --diagnostics")
+    new.add_argument("--diagnostic-batch-means", action='store_true', default=False, help="--diagnostics: also ESS and MCSE by batch means on a "
+                     "dyadic ladder of batch sizes, for columns whose autocorrelation time exceeds --diagnostic-lags; written to the summary "
+                     "JSON as \"batch_means\" inside \"diagnostics\"")
     new.add_argument("--waic", action='store_true', default=False, help="WAIC, p_waic and the pointwise elpd of every data point over all "
                      "chains' post-burn-in draws, accumulated on the GPU while the rows stream past; written to the summary JSON as \"waic\"")
     new.add_argument("--loo", action='store_true', default=False, help="PSIS-LOO: elpd_loo, p_loo and the Pareto k-hat of every data point over "
@@ -301,6 +306,13 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         diag = dg.ChainDiagnostics(Q, C, d + 1, diag_rows, args.diagnostic_lags, device)
         if burn == 0:
             diag.accumulate(s.row0.unsqueeze(0).contiguous())
+    bmeans = None
+    if getattr(args, "diagnostic_batch_means", False):
+        from . import batch_means as bm
+        bm.check_memory(bm.workspace_bytes(Q, d + 1, C, saved_iterations - burn), device)
+        bmeans = bm.BatchMeans(Q, C, d + 1, saved_iterations - burn, device)
+        if burn == 0:
+            bmeans.accumulate(s.row0.unsqueeze(0).contiguous())
     waic = None
     if getattr(args, "waic", False):
         from . import waic as wc
@@ -361,6 +373,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         first = max(0, burn - r)                                       # saved rows before `burn` are the burn-in
         if diag is not None and first < nr:
             diag.accumulate(rows[first:])
+        if bmeans is not None and first < nr:
+            bmeans.accumulate(rows[first:])
         if waic is not None and first < nr:
             waic.accumulate(rows[first:])
         if psis is not None and first < nr:
@@ -381,6 +395,9 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     mean, var = mean.cpu().numpy(), var.cpu().numpy()
     acc = s.acceptance().cpu().numpy()
     diag_res = diag.result() if diag is not None else None
+    bm_res = bmeans.result() if bmeans is not None else None
+    if bmeans is not None:
+        bmeans.free()
     waic_res = waic.result() if waic is not None else None
     loo_res = psis.result() if psis is not None else None
     if psis is not None:
@@ -410,6 +427,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
                 "mh_samples_per_second": Q * C * total_iterations / elapsed}
         if diag_res is not None:
             summ["diagnostics"] = dg.json_record(diag_res, q, args.diagnostic_lags, saved_iterations - burn, C)
+            if bm_res is not None:
+                summ["diagnostics"]["batch_means"] = bm.json_record(bm_res, q)
         if waic_res is not None:
             summ["waic"] = wc.json_record(waic_res[q], wpts, q)
         if loo_res is not None:
@@ -429,6 +448,8 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     writers.close()
     if diag_res is not None:
         print(dg.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], diag_res["rhat"], diag_res["ess"]))
+    if bm_res is not None:
+        print(bm.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], diag_res["ess"], bm_res["ess"], bm_res["tau"], thinning))
     if waic_res is not None:
         print(wc.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], waic_res))
     if loo_res is not None:

@@ -55,6 +55,9 @@ def build_parser():
     new.add_argument("--diagnostics", action='store_true', default=False, help="split-R-hat, multi-chain ESS and MCSE of every column of every rung over "
                      "all chains, accumulated on the GPU; written to thermodynamic_integration.json (one object per rung) and the rung records")
     new.add_argument("--diagnostic-lags", type=int, default=256, help="lag limit K of the autocorrelation sums of --diagnostics")
+    new.add_argument("--diagnostic-batch-means", action='store_true', default=False, help="--diagnostics: also ESS and MCSE by batch means on a "
+                     "dyadic ladder of batch sizes, for rungs whose autocorrelation time exceeds --diagnostic-lags; written as "
+                     "\"batch_means\" inside each \"diagnostics\" object")
     new.add_argument("--stepping-stone", action='store_true', default=False, help="stepping-stone estimate of log Z (Xie et al. 2011) "
                      "with standard errors and per-rung importance-weight ESS, accumulated on the GPU from the same rows; written to "
                      "thermodynamic_integration.json (\"stepping_stone\") and the rung records")
@@ -126,6 +129,19 @@ def attach_diagnostics(rungs, tis, unit_rows, width, cols, R, chains, total_rows
         rec["diagnostics"] = dg.json_record(res, u, lags, total_rows, chains, columns=dr.file_labels + ["log-target"])
     for ip, ti in enumerate(tis):
         ti["diagnostics"] = [rungs[ip * R + ir]["diagnostics"] for ir in range(R)]
+
+
+def attach_batch_means(rungs, unit_rows, first, cols):
+    """the gathered per-unit batch-means values (columns first.. of unit_rows: batch_means.FIELDS per column) into the "diagnostics"
+    object of every rung record (the pair records hold the same objects)"""
+    from . import batch_means as bm
+    unit_rows = unit_rows[np.lexsort((unit_rows[:, 1], unit_rows[:, 0]))]
+    v = unit_rows[:, first:first + len(bm.FIELDS) * cols].reshape(len(unit_rows), len(bm.FIELDS), cols)
+    res = {k: v[:, i] for i, k in enumerate(bm.FIELDS)}
+    for k in ("plateau_reached", "chains_agree"):
+        res[k] = res[k] != 0
+    for u, rec in enumerate(rungs):
+        rec["diagnostics"]["batch_means"] = bm.json_record(res, u)
 
 
 def attach_stepping_stone(rungs, tis, unit_rows, first, temperatures, chains):
@@ -206,6 +222,10 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     if swap > 0:                  # per unit: replica_exchange.UNIT_COLUMNS; they ride on the same gather
         from . import replica_exchange as rxm
         unit_rows = np.concatenate([unit_rows, np.zeros((len(mine), len(rxm.UNIT_COLUMNS)))], axis=1)
+    bm_first = unit_rows.shape[1]
+    if args.diagnostic_batch_means:   # per unit and column: batch_means.FIELDS; they ride on the same gather
+        from . import batch_means as bm
+        unit_rows = np.concatenate([unit_rows, np.zeros((len(mine), len(bm.FIELDS) * (d + 1)))], axis=1)
     # the rows the fused <log L(t=1)> counts: saved rows with t > moments_after, i.e. row index >= max(burn, 1)
     first_kept = max(burn, 1)
     mcmc_time = 0.0
@@ -234,6 +254,12 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
             diag = dg.ChainDiagnostics(Q, C, d + 1, num_saved - burn, args.diagnostic_lags, device)
             if burn == 0:
                 diag.accumulate(s.row0.unsqueeze(0).contiguous())
+        bmeans = None
+        if args.diagnostic_batch_means:
+            bm.check_memory(bm.workspace_bytes(Q, d + 1, C, num_saved - burn), device)
+            bmeans = bm.BatchMeans(Q, C, d + 1, num_saved - burn, device)
+            if burn == 0:
+                bmeans.accumulate(s.row0.unsqueeze(0).contiguous())
         sst = None
         if args.stepping_stone:
             delta = ss.deltas(temperatures)
@@ -249,6 +275,8 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
             first = max(0, burn - r)                                    # saved rows before `burn` are the burn-in
             if diag is not None and first < nr:
                 diag.accumulate(rows[first:])
+            if bmeans is not None and first < nr:
+                bmeans.accumulate(rows[first:])
             first = max(0, first_kept - r)
             if sst is not None and first < nr:
                 sst.accumulate(rows[first:])
@@ -262,14 +290,20 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
         ll1 = s.mean_log_likelihood_t1().cpu().numpy()            # [Q][C]  E_rung[log L(theta; t=1)], fused into the sampler
         if diag is not None:
             res = diag.result()
-            unit_rows[:, width:] = np.concatenate([res["rhat"], res["ess"], res["mcse_mean"], res["lag_limit_reached"].astype(np.float64)], axis=1)
+            unit_rows[:, width:ss_first] = np.concatenate([res["rhat"], res["ess"], res["mcse_mean"], res["lag_limit_reached"].astype(np.float64)], axis=1)
             print(dg.report_line(rank, ["{} + {} at t = {:g}".format(loaded[int(u) // R][0], loaded[int(u) // R][1], temperatures[int(u) % R])
                                         for u in mine], res["rhat"], res["ess"]))
+        if bmeans is not None:
+            bres = bmeans.result()
+            bmeans.free()
+            unit_rows[:, bm_first:] = np.concatenate([np.asarray(bres[k], dtype=np.float64) for k in bm.FIELDS], axis=1)
+            print(bm.report_line(rank, ["{} + {} at t = {:g}".format(loaded[int(u) // R][0], loaded[int(u) // R][1], temperatures[int(u) % R])
+                                        for u in mine], res["ess"], bres["ess"], bres["tau"], thinning))
         if sst is not None:
             unit_rows[:, ss_first:ss_first + len(ss.OUT)] = sst.reduced()
         if rx is not None:
             se_joint = rxm.joint_se(sst, len(my_pairs), R) if sst is not None else None
-            unit_rows[:, rx_first:] = rxm.unit_columns(rx.statistics(), rx.rounds, len(my_pairs), R, se_joint,
+            unit_rows[:, rx_first:bm_first] = rxm.unit_columns(rx.statistics(), rx.rounds, len(my_pairs), R, se_joint,
                                                        rxm.replica_set_ti_se(ll1, temperatures, len(my_pairs)))
         if sst is not None:
             sst.free()
@@ -292,6 +326,8 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     out, tis = assemble_thermodynamic_integration(gathered[:, :width], [(l[0], l[1]) for l in loaded], temperatures, model, facts)
     if args.diagnostics:
         attach_diagnostics(out, tis, gathered[:, :ss_first], width, d + 1, R, C, num_saved - burn, args.diagnostic_lags)
+    if args.diagnostic_batch_means:
+        attach_batch_means(out, gathered, bm_first, d + 1)
     ss_recs = None
     if args.stepping_stone:
         ss_recs = attach_stepping_stone(out, tis, gathered, ss_first, temperatures, C)
@@ -328,6 +364,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.swap_every < 0:
         parser.error("--swap-every must be 0 (off) or a positive number of iterations")
+    if args.diagnostic_batch_means and not args.diagnostics:
+        parser.error("--diagnostic-batch-means needs --diagnostics")
     n = phfdist.ranks_for_cores(args.num_cores)                         # -nc N: the reference's pool over the rungs (:155-159) -> N ranks
     if n:
         sys.exit(phfdist.spawn_ranks("pyhillfit_amd.PyHillTemp", sys.argv[1:] if argv is None else argv, n))

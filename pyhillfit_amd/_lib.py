@@ -26,7 +26,8 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_replica_exchange_stats_bytes", "phf_replica_exchange_stats_init", "phf_replica_exchange_stats_read",
            "phf_replica_exchange_labels_init", "phf_replica_exchange_round", "phf_hier_de_workspace_bytes", "phf_hier_de_stats_bytes",
            "phf_hier_de_stats_init", "phf_hier_de_stats_read", "phf_hier_de_round", "phf_sensitivity_workspace_bytes", "phf_sensitivity_init",
-           "phf_sensitivity_accumulate", "phf_sensitivity_reduce", "phf_sensitivity_components"]
+           "phf_sensitivity_accumulate", "phf_sensitivity_reduce", "phf_sensitivity_components", "phf_batch_means_workspace_bytes",
+           "phf_batch_means_levels", "phf_batch_means_init", "phf_batch_means_accumulate", "phf_batch_means_reduce"]
 
 
 class PhfError(RuntimeError):
@@ -164,6 +165,12 @@ def load():
     lib.phf_sensitivity_accumulate.argtypes = [i32, vp, vp, vp, i32, i32, vp, i64, i32, i32, i32, i32, f64, i32, i64, i64, vp, C.c_size_t, vp]
     lib.phf_sensitivity_reduce.argtypes = [i32, i32, i32, i64, i32, vp, C.c_size_t, vp, vp, vp, vp, vp]
     lib.phf_sensitivity_components.argtypes = [i32, vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.phf_batch_means_workspace_bytes.argtypes = [i32, i32, i32, i64]
+    lib.phf_batch_means_workspace_bytes.restype = C.c_size_t
+    lib.phf_batch_means_levels.argtypes = [i64]
+    lib.phf_batch_means_init.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp]
+    lib.phf_batch_means_accumulate.argtypes = [vp, i64, i32, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
+    lib.phf_batch_means_reduce.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
     _lib = lib
     return lib
 

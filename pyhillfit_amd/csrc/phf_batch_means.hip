@@ -1,0 +1,200 @@
+// phf_batch_means.hip — ESS and MCSE beyond the lag limit: batch means on a dyadic ladder of batch sizes for every
+// (problem, column, chain), accumulated while the rows stream past (the routine itself: phf_batch_means.h; the estimator on the
+// host: pyhillfit_amd/batch_means.py; DESIGN.md §3, "ESS beyond the lag limit").
+//
+// Accumulate kernel: one lane = one chain, a wavefront = 64 chains of one (problem, column); the rows are [rows][Q][stride][C], chain
+// fastest, so a wavefront reads 512 contiguous bytes per row and the state (chain fastest as well) moves in the same lines.  Aligned
+// groups of 32 rows are unrolled: levels 0..4 and their pending sums sit in registers under compile-time indices, levels >= 5 are
+// touched in HBM once per 32 rows; the unaligned head and tail of a sub-segment go row by row against HBM.  The host cuts a segment
+// at the half-chain boundary, so a launch sees rows of one half-chain only.  No atomics, no LDS, no cross-lane traffic; every
+// accumulator round-trips through HBM exactly, so the state is bit-identical however the rows are cut into calls.
+//
+// Reduce kernel: one wavefront per (problem, column, level with n_l = floor(h / 2^l) >= 2 batches), plus one per (problem, column) for
+// the half-chain means.  Lane l adds chains l, l + 64, ... (half 0's term, then half 1's), then a fixed butterfly (xor 32, 16, .., 1).
+#include <hip/hip_runtime.h>
+
+#include "../../include/pyhillfit_amd.h"
+#include "phf_batch_means.h"
+#include "phf_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+
+struct BmArgs {
+  const double* rows;             // first row of this sub-segment: [nr][Q][stride][C]
+  int64_t nr;                     // rows in this sub-segment (all in one half-chain)
+  int64_t m0;                     // half-chain index of its first row
+  int64_t h;
+  int32_t Q, stride, C, cols, nl, half, ncg;
+  int64_t units;
+  double* ws;                     // [Q][cols][5 nl + 2][C]
+  double* out;                    // reduce: [Q][cols][nl + 1]
+};
+
+__global__ __launch_bounds__(kThreads) void batch_means_accumulate_kernel(const BmArgs a) {
+  const int64_t unit = (int64_t)blockIdx.x * kWaves + threadIdx.x / 64;
+  if (unit >= a.units) return;
+  const int cg = (int)(unit % a.ncg);
+  const int64_t qj = unit / a.ncg;
+  const int j = (int)(qj % a.cols), q = (int)(qj / a.cols);
+  const int c = cg * 64 + (threadIdx.x & 63);
+  if (c >= a.C) return;
+  const size_t rstep = (size_t)a.Q * a.stride * a.C;
+  const double* xr = a.rows + ((size_t)q * a.stride + j) * a.C + c;
+  double* st = a.ws + (size_t)qj * PHF_BM_FIELDS(a.nl) * a.C + c;
+  phf_bm_rows(xr, rstep, a.nr, a.m0, a.half, st, (size_t)a.C, a.nl);
+}
+
+__device__ inline double wave_sum(double v) {
+  _Pragma("unroll")
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// out[q][j][l] = mean over the 2C half-chains of the variance of the batch means of level l, l = 0..nl-2 (l = 0: W);
+// out[q][j][nl-1] = mean of the half-chain means; out[q][j][nl] = their variance (divisor 2C - 1) = B/h
+__global__ __launch_bounds__(kThreads) void batch_means_reduce_kernel(const BmArgs a) {
+  const int64_t unit = (int64_t)blockIdx.x * kWaves + threadIdx.x / 64;
+  if (unit >= a.units) return;
+  const int lane = threadIdx.x & 63;
+  const int nl = a.nl;
+  const int k = (int)(unit % nl);
+  const int64_t qj = unit / nl;
+  const double* st = a.ws + (size_t)qj * PHF_BM_FIELDS(nl) * a.C;
+  const size_t C = (size_t)a.C;
+  const double M = 2.0 * a.C;
+  double* o = a.out + (size_t)qj * (nl + 1);
+  if (k < nl - 1) {
+    const double n = (double)(a.h >> k), b = (double)((int64_t)1 << k);
+    double s = 0.0;
+    for (int c = lane; c < a.C; c += 64) {
+      const double v0 = phf_bm_block_mean_variance(st[(size_t)phf_bm_s1(nl, 0, k) * C + c], st[(size_t)phf_bm_s2(nl, 0, k) * C + c], n, b);
+      const double v1 = phf_bm_block_mean_variance(st[(size_t)phf_bm_s1(nl, 1, k) * C + c], st[(size_t)phf_bm_s2(nl, 1, k) * C + c], n, b);
+      s += v0 + v1;
+    }
+    s = wave_sum(s);
+    if (lane == 0) o[k] = s / M;
+  } else {
+    const double hd = (double)a.h;
+    double s = 0.0;
+    for (int c = lane; c < a.C; c += 64) {
+      const double m0 = st[(size_t)phf_bm_x0(0) * C + c] + st[(size_t)phf_bm_s1(nl, 0, 0) * C + c] / hd;
+      const double m1 = st[(size_t)phf_bm_x0(1) * C + c] + st[(size_t)phf_bm_s1(nl, 1, 0) * C + c] / hd;
+      s += m0 + m1;
+    }
+    const double mean = wave_sum(s) / M;
+    double v = 0.0;
+    for (int c = lane; c < a.C; c += 64) {
+      const double d0 = st[(size_t)phf_bm_x0(0) * C + c] + st[(size_t)phf_bm_s1(nl, 0, 0) * C + c] / hd - mean;
+      const double d1 = st[(size_t)phf_bm_x0(1) * C + c] + st[(size_t)phf_bm_s1(nl, 1, 0) * C + c] / hd - mean;
+      v += d0 * d0 + d1 * d1;
+    }
+    v = wave_sum(v);
+    if (lane == 0) { o[nl - 1] = mean; o[nl] = v / (M - 1.0); }
+  }
+}
+
+unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+
+// shared argument checks of the four entries; on success *nl = floor(log2 h) + 1
+int check_shape(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows, int* nl) {
+  char msg[kPhfErrorBufferSize];
+  if (num_problems < 1 || num_columns < 1 || num_chains < 1) {
+    std::snprintf(msg, sizeof msg, "%s: num_problems, num_columns and num_chains must be positive", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  if (total_rows < 4) {
+    std::snprintf(msg, sizeof msg, "%s: a half-chain needs h = floor(total_rows / 2) >= 2 rows (total_rows = %lld)", who, (long long)total_rows);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  *nl = phf_bm_levels(total_rows / 2);
+  const double units = (double)num_problems * num_columns * ((num_chains + 63) / 64 > *nl ? (num_chains + 63) / 64 : *nl);
+  if (units / kWaves > 2147483647.0) {
+    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  }
+  return PHF_OK;
+}
+
+size_t workspace_bytes_of(int num_problems, int num_columns, int num_chains, int nl) {
+  return (size_t)num_problems * num_columns * (size_t)PHF_BM_FIELDS(nl) * num_chains * sizeof(double);
+}
+
+}  // namespace
+
+extern "C" size_t phf_batch_means_workspace_bytes(int num_problems, int num_columns, int num_chains, int64_t total_rows) {
+  int nl;
+  if (check_shape("phf_batch_means_workspace_bytes", num_problems, num_columns, num_chains, total_rows, &nl) != PHF_OK) return 0;
+  return workspace_bytes_of(num_problems, num_columns, num_chains, nl);
+}
+
+extern "C" int phf_batch_means_levels(int64_t total_rows) {
+  if (total_rows < 4) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_levels: need total_rows >= 4");
+  return phf_bm_levels(total_rows / 2);
+}
+
+extern "C" int phf_batch_means_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, double* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  int nl;
+  int rc = check_shape("phf_batch_means_init", num_problems, num_columns, num_chains, total_rows, &nl);
+  if (rc != PHF_OK) return rc;
+  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_init: null workspace");
+  const size_t need = workspace_bytes_of(num_problems, num_columns, num_chains, nl);
+  if (workspace_bytes < need) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_init: workspace smaller than phf_batch_means_workspace_bytes()");
+  if ((rc = phf_require_device_memory(workspace, "phf_batch_means_init: workspace")) != PHF_OK) return rc;
+  if (hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch("phf_batch_means_init");
+  return PHF_OK;
+}
+
+extern "C" int phf_batch_means_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                                          int num_columns, int64_t first_row, int64_t total_rows, double* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  static const char* who = "phf_batch_means_accumulate";
+  int nl;
+  int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows, &nl);
+  if (rc != PHF_OK) return rc;
+  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
+  if (row_stride_cols < num_columns)
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: row_stride_cols must be >= num_columns");
+  if (!rows || !workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: null pointer");
+  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains, nl))
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: workspace smaller than phf_batch_means_workspace_bytes()");
+  if (num_rows == 0) return PHF_OK;
+  BmArgs a = {};
+  a.Q = num_problems; a.stride = row_stride_cols; a.C = num_chains; a.cols = num_columns; a.nl = nl; a.ws = workspace;
+  a.h = total_rows / 2;
+  a.ncg = (num_chains + 63) / 64;
+  a.units = (int64_t)num_problems * num_columns * a.ncg;
+  const size_t row_doubles = (size_t)num_problems * row_stride_cols * num_chains;
+  const int64_t half_begin[2] = {0, total_rows - a.h};
+  for (int half = 0; half < 2; ++half) {
+    const int64_t lo = first_row > half_begin[half] ? first_row : half_begin[half];
+    const int64_t end = first_row + num_rows, hend = half_begin[half] + a.h;
+    const int64_t hi = end < hend ? end : hend;
+    if (lo >= hi) continue;
+    a.rows = rows + (size_t)(lo - first_row) * row_doubles;
+    a.nr = hi - lo; a.m0 = lo - half_begin[half]; a.half = half;
+    hipLaunchKernelGGL(batch_means_accumulate_kernel, dim3(blocks_for(a.units, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+    if ((rc = phf_check_launch("batch_means_accumulate_kernel")) != PHF_OK) return rc;
+  }
+  return PHF_OK;
+}
+
+extern "C" int phf_batch_means_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, const double* workspace,
+                                      size_t workspace_bytes, double* out, void* stream) {
+  int nl;
+  int rc = check_shape("phf_batch_means_reduce", num_problems, num_columns, num_chains, total_rows, &nl);
+  if (rc != PHF_OK) return rc;
+  if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_reduce: null pointer");
+  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains, nl))
+    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_reduce: workspace smaller than phf_batch_means_workspace_bytes()");
+  BmArgs a = {};
+  a.Q = num_problems; a.C = num_chains; a.cols = num_columns; a.nl = nl; a.h = total_rows / 2;
+  a.ws = const_cast<double*>(workspace); a.out = out;
+  a.units = (int64_t)num_problems * num_columns * nl;
+  hipLaunchKernelGGL(batch_means_reduce_kernel, dim3(blocks_for(a.units, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  return phf_check_launch("batch_means_reduce_kernel");
+}

@@ -589,6 +589,13 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             diag = dg.ChainDiagnostics(Q, C, d + 1, saved_iterations - burn, args.diagnostic_lags, device)
             if burn == 0:
                 diag.accumulate(s.row0.unsqueeze(0).contiguous())
+        bmeans = None
+        if getattr(args, "diagnostic_batch_means", False):             # ESS / MCSE by batch means, fed exactly where the diagnostics are
+            from . import batch_means as bm
+            bm.check_memory(bm.workspace_bytes(Q, d + 1, C, saved_iterations - burn), device)
+            bmeans = bm.BatchMeans(Q, C, d + 1, saved_iterations - burn, device)
+            if burn == 0:
+                bmeans.accumulate(s.row0.unsqueeze(0).contiguous())
         waic = None
         if getattr(args, "waic", False):                               # WAIC over all chains, accumulated like the diagnostics
             from . import waic as wc
@@ -652,7 +659,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             if burn == 0:
                 sens.accumulate(s.row0.unsqueeze(0).contiguous())
         runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, waic=waic, psis=psis, logo=logo, quant=quant, ppc=ppc, sens=sens,
+                         diag=diag, bmeans=bmeans, waic=waic, psis=psis, logo=logo, quant=quant, ppc=ppc, sens=sens,
                          stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
@@ -704,6 +711,8 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     run["curves"].accumulate(rows[first:], cdf_chains(args, args.num_chains))
                 if run["diag"] is not None and first < nr:
                     run["diag"].accumulate(rows[first:])
+                if run["bmeans"] is not None and first < nr:
+                    run["bmeans"].accumulate(rows[first:])
                 if run["waic"] is not None and first < nr:
                     run["waic"].accumulate(rows[first:])
                 if run["psis"] is not None and first < nr:
@@ -740,6 +749,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     sens_names, sens_parts = [], []
     logo_names, logo_parts, logo_labels = [], [], []
     de_names, de_parts = [], []
+    bm_parts = []
     band_nf = 0
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
@@ -750,6 +760,9 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         diag_res = run["diag"].result() if run["diag"] is not None else None
         if diag_res is not None:
             run["diag"].free()
+        bm_res = run["bmeans"].result() if run["bmeans"] is not None else None
+        if bm_res is not None:
+            run["bmeans"].free()
         waic_res = run["waic"].result() if run["waic"] is not None else None
         loo_res = run["psis"].result() if run["psis"] is not None else None
         if loo_res is not None:
@@ -789,6 +802,10 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
                     from . import de_moves as de
                     summ["diagnostics"]["chains_coupled_within_populations_of"] = s.de.G
                     summ["diagnostics"]["note"] = de.COUPLING_NOTE.format(G=s.de.G)
+                if bm_res is not None:
+                    from . import batch_means as bm
+                    summ["diagnostics"]["batch_means"] = bm.json_record(bm_res, q, de_coupled=de_res is not None)
+                    bm_parts.append((bm_res["ess"][q], bm_res["tau"][q]))
             if de_res is not None:
                 summ["de_moves"] = de_res[q]
                 de_names.append("{} + {}".format(d_clean, c_clean))
@@ -840,6 +857,12 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         if getattr(args, "de_every", 0):
             from . import de_moves as de
             print("diagnostics [rank {}]: {}".format(rank, de.COUPLING_NOTE.format(G=args.de_population)))
+        if getattr(args, "diagnostic_batch_means", False):
+            from . import batch_means as bm
+            print(bm.report_line(rank, diag_names, [p_[1] for p_ in diag_parts], [p_[0] for p_ in bm_parts], [p_[1] for p_ in bm_parts],
+                                 thinning))
+            if getattr(args, "de_every", 0):
+                print("batch means [rank {}]: {}".format(rank, bm.DE_NOTE))
     if getattr(args, "de_every", 0):
         from . import de_moves as de
         print(de.report_line(rank, de_names, de_parts))
