@@ -234,6 +234,123 @@ PHF_HD void phf_sl_log_target_shared(int model, const double* lc, const double* 
   const double lp = -PHF_PIC50_RATE * pic50 + g;
   *out_prior = outside ? -PHF_INF : lp;
 }
+
+/* phf_sl_log_target_shared for the samplers' steady iteration: the same arguments and the same fp64 operations in the same order,
+ * WITHOUT the two -inf selects.  It returns `outside` — the prior's combined predicate, as above — and leaves in out_lik, out_prior,
+ * out_ll1 and out_lt (= lik + prior) the values the selects would have replaced; the caller rejects an `outside` proposal by the
+ * predicate:  accept = !outside & (accept test on out_lt - lt).
+ * Exact, case by case (x = lt_star - lt is the accept test's argument; both tests reject -inf and NaN):
+ *   outside, lt finite: phf_sl_log_target_shared gives prior = -inf, so lt_star = lik + -inf is -inf or NaN for every lik (finite,
+ *     +-inf, NaN, or the 0 of temperature 0), x is -inf or NaN and the test rejects: what the predicate does here.
+ *   outside, lt = -inf (a start outside the support): lt_star is again -inf or NaN, x = lt_star + inf is NaN: reject, likewise.
+ *   sigma <= PHF_SIGMA_FLOOR (the likelihood's -inf): floor and PHF_SIGMA_LOC are one double (asserted below), so this IS `outside`.
+ *   not outside: neither select changes a value there either; lik, prior, ll1 are the same doubles (a NaN theta compares false
+ *     everywhere, is not `outside` in either version and runs the same arithmetic).
+ * theta, lt and ll1 are taken over only on accept, so the unselected values of a rejected proposal are never seen.
+ * lower_clamp == 0 promises that every ln_conc of the pair is >= PHF_LN_CONC_NOCLAMP: the Hill denominators' exponentials then skip
+ * the lower clamp fmax(a, -746) of phf_exp_capped_k, which cannot fire inside the support: there hill is in [0, PHF_HILL_UPPER] and
+ * pic50 >= PHF_PIC50_LOWER, so ln_ic50 <= 9 ln 10 = 20.8 and the argument a = hill (ln_conc - ln_ic50) >= 10 (-50 - 20.8) = -708 (model 1:
+ * >= -70.8), far above -746 (fmax(a, -746) = a: the same double).  Outside the support the exponential may return anything — the
+ * proposal is rejected by the predicate — and its table index is masked (phf_exp_core_k: n & 63), so no address depends on it.  A NaN
+ * argument is still dropped by the upper cap fmin(a, PHF_HILL_ARG_CAP), which stays. */
+#define PHF_LN_CONC_NOCLAMP (-50.0)
+#if defined(__cplusplus)
+static_assert(PHF_SIGMA_FLOOR == PHF_SIGMA_LOC, "sigma <= floor must imply outside");
+#else
+_Static_assert(PHF_SIGMA_FLOOR == PHF_SIGMA_LOC, "sigma <= floor must imply outside");
+#endif
+PHF_HD double phf_hill_den_sampler(int model, double ln_conc, double hill, double ln_ic50, int lower_clamp, phf_ktab k_exp) {
+  const double a = (model == 1) ? (ln_conc - ln_ic50) : hill * (ln_conc - ln_ic50);
+  const double c = __builtin_fmin(a, PHF_HILL_ARG_CAP);
+  return 1.0 + (lower_clamp ? phf_exp_capped_k(c, k_exp) : phf_exp_core_k(c, k_exp));
+}
+#define PHF_DEN_(jj) phf_hill_den_sampler(model, lc[jj], hill, ln_ic50, lower_clamp, k_exp)
+#define PHF_CDEN_S_(jj) ((((share_mask) >> ((jj) - n_other)) & 1u) ? den_slot[den_off[(jj) - n_other]] : PHF_DEN_(jj))
+PHF_HD int phf_sl_log_target_sampler(int model, const double* lc, const double* y, const double* w, int n_other, int n_cens,
+                                     double n_other_points, double ss_within, double pi_bit, double temperature, int lower_clamp,
+                                     const double* th, phf_ktab k_exp, phf_ktab k_log,
+                                     unsigned share_mask, const int* den_off, double* den_slot, int slot_stride,
+                                     double* out_lik, double* out_prior, double* out_ll1, double* out_lt) {
+  const double pic50 = th[0];
+  const double hill = (model == 1) ? 1.0 : th[1];
+  const double sigma = (model == 1) ? th[1] : th[2];
+  const double ln_ic50 = PHF_LN10 * (6.0 - pic50);
+  const double sl = sigma - PHF_SIGMA_LOC;
+  const double inv_s = phf_rcp(sigma);
+  const double log_sigma = phf_log_pos_k(sigma, k_log);
+  const double log_sl = phf_log_pos_k(sl, k_log);
+
+  double sse = ss_within, cens = 0.0;
+  int j = 0;
+  for (; j + 4 <= n_other; j += 4) {
+    const double d0 = PHF_DEN_(j), d1 = PHF_DEN_(j + 1);
+    const double d2 = PHF_DEN_(j + 2), d3 = PHF_DEN_(j + 3);
+    PHF_SHARE_PUT_(j, d0); PHF_SHARE_PUT_(j + 1, d1); PHF_SHARE_PUT_(j + 2, d2); PHF_SHARE_PUT_(j + 3, d3);
+    const double p01 = d0 * d1, p23 = d2 * d3;
+    const double inv = phf_rcp(p01 * p23);
+    const double i01 = inv * p23, i23 = inv * p01;
+    const double r0 = y[j] - PHF_PCT_(i01 * d1), r1 = y[j + 1] - PHF_PCT_(i01 * d0);
+    const double r2 = y[j + 2] - PHF_PCT_(i23 * d3), r3 = y[j + 3] - PHF_PCT_(i23 * d2);
+    sse = phf_fma(w[j] * r0, r0, sse); sse = phf_fma(w[j + 1] * r1, r1, sse);
+    sse = phf_fma(w[j + 2] * r2, r2, sse); sse = phf_fma(w[j + 3] * r3, r3, sse);
+  }
+  const int rem = n_other - j;
+  if (rem == 3) {
+    const double d0 = PHF_DEN_(j), d1 = PHF_DEN_(j + 1);
+    const double d2 = PHF_DEN_(j + 2);
+    PHF_SHARE_PUT_(j, d0); PHF_SHARE_PUT_(j + 1, d1); PHF_SHARE_PUT_(j + 2, d2);
+    const double p01 = d0 * d1;
+    const double inv = phf_rcp(p01 * d2);
+    const double i01 = inv * d2;
+    const double r0 = y[j] - PHF_PCT_(i01 * d1), r1 = y[j + 1] - PHF_PCT_(i01 * d0);
+    const double r2 = y[j + 2] - PHF_PCT_(inv * p01);
+    sse = phf_fma(w[j] * r0, r0, sse); sse = phf_fma(w[j + 1] * r1, r1, sse); sse = phf_fma(w[j + 2] * r2, r2, sse);
+  } else if (rem == 2) {
+    const double d0 = PHF_DEN_(j), d1 = PHF_DEN_(j + 1);
+    PHF_SHARE_PUT_(j, d0); PHF_SHARE_PUT_(j + 1, d1);
+    const double inv = phf_rcp(d0 * d1);
+    const double r0 = y[j] - PHF_PCT_(inv * d1), r1 = y[j + 1] - PHF_PCT_(inv * d0);
+    sse = phf_fma(w[j] * r0, r0, sse); sse = phf_fma(w[j + 1] * r1, r1, sse);
+  } else if (rem == 1) {
+    const double d0 = PHF_DEN_(j);
+    PHF_SHARE_PUT_(j, d0);
+    const double r = y[j] - PHF_PCT_(phf_rcp(d0));
+    sse = phf_fma(w[j] * r, r, sse);
+  }
+  j = n_other;
+  const int n = n_other + n_cens;
+  for (; j + 2 <= n; j += 2) {
+    const double d0 = PHF_CDEN_S_(j), d1 = PHF_CDEN_S_(j + 1);
+    const double inv = phf_rcp(d0 * d1);
+    const double z0 = phf_censored_z(PHF_PCT_(inv * d1), y[j], inv_s);
+    const double z1 = phf_censored_z(PHF_PCT_(inv * d0), y[j + 1], inv_s);
+    cens = phf_fma(w[j], phf_log_ndtr_tab(z0, -z0 * PHF_INV_SQRT2), cens);
+    cens = phf_fma(w[j + 1], phf_log_ndtr_tab(z1, -z1 * PHF_INV_SQRT2), cens);
+  }
+  for (; j < n; ++j) {
+    const double pred = PHF_PCT_(phf_rcp(PHF_CDEN_S_(j)));
+    const double z = phf_censored_z(pred, y[j], inv_s);
+    cens = phf_fma(w[j], phf_log_ndtr_tab(z, -z * PHF_INV_SQRT2), cens);
+  }
+  double a = cens - pi_bit;
+  a = phf_fma(-n_other_points, log_sigma, a);
+  a = phf_fma(-sse, 0.5 * inv_s * inv_s, a);
+  *out_ll1 = a;
+
+  const int outside = (pic50 < PHF_PIC50_LOWER)
+                      | (sigma <= PHF_SIGMA_LOC)
+                      | ((model == 2) & ((hill < 0.0) | (hill > PHF_HILL_UPPER)));
+  const double g = phf_fma(PHF_SIGMA_SHAPE_M1, log_sl, -sl * PHF_SIGMA_INV_SCALE);
+  const double lp = -PHF_PIC50_RATE * pic50 + g;
+  *out_prior = lp;
+  double lik = temperature * a;
+  if (temperature == 0.0) lik = 0.0;
+  *out_lik = lik;
+  *out_lt = lik + lp;
+  return outside;
+}
+#undef PHF_DEN_
+#undef PHF_CDEN_S_
 #undef PHF_SHARE_PUT_
 #undef PHF_CDEN_
 

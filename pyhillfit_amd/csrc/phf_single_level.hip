@@ -62,6 +62,45 @@ __device__ __forceinline__ void chol_packed(const double* c, double* l) {
   }
 }
 
+// Same-source A/B builds of the steady bodies' parts (tools/build_exp_sl.sh ... -DPHF_SL_STEADY_CHOL=0): 0 keeps the parent's form
+#ifndef PHF_SL_STEADY_CHOL
+#define PHF_SL_STEADY_CHOL 1       // the pivots' selects under a wave-uniform test (chol_packed_steady)
+#endif
+#ifndef PHF_SL_STEADY_NOCLAMP
+#define PHF_SL_STEADY_NOCLAMP 1    // straight-line bodies without the Hill exponentials' lower clamp (run_block sends other pairs elsewhere)
+#endif
+// chol_packed for the steady bodies: the same operations without the pivots' selects, which change a value only where a pivot is not
+// positive.  The predicates stay (!(s > 0): a NaN pivot counts), and when ANY lane of the wavefront has such a pivot the guarded
+// version above runs and every lane that has one takes ITS whole factor.  A lane whose pivots are all positive has selected nothing
+// in the guarded version either: the same doubles.  The unguarded values of a lane with a bad pivot (NaN, infinities) never leave here.
+template <int D>
+__device__ __forceinline__ void chol_packed_steady(const double* c, double* l) {
+  double inv[D];
+  bool bad = false;
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      double s = c[i * (i + 1) / 2 + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s = phf_fma(-l[i * (i + 1) / 2 + k], l[j * (j + 1) / 2 + k], s);
+      if (i == j) {
+        bad |= !(s > 0.0);
+        inv[i] = 0.0;
+        l[i * (i + 1) / 2 + i] = (i + 1 < D) ? phf_sqrt_rcp_pos(s, &inv[i]) : phf_sqrt_pos(s);
+      } else {
+        l[i * (i + 1) / 2 + j] = s * inv[j];
+      }
+    }
+  }
+  if (PHF_ANY_LANE(bad)) {                                  // wave-uniform and rare: a degenerate or non-finite covariance
+    double lg[D * (D + 1) / 2];
+    chol_packed<D>(c, lg);
+#pragma unroll
+    for (int i = 0; i < D * (D + 1) / 2; ++i) l[i] = bad ? lg[i] : l[i];
+  }
+}
+
 struct AdvanceArgs {
   phf_points pts;
   phf_problems prob;
@@ -110,6 +149,9 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
                 "shared denominators need a straight-line body with at most kDenSlots uncensored entries");
   constexpr int D = Dim<MODEL>::d;
   constexpr int NTRI = D * (D + 1) / 2;
+  // the straight-line steady bodies run only pairs whose every ln_conc is >= PHF_LN_CONC_NOCLAMP (run_block) and drop the lower clamp of
+  // the Hill exponentials (phf_sl_log_target_sampler); the run-time-loop body serves every pair and keeps it
+  constexpr int kLowerClamp = !(PHF_SL_STEADY_NOCLAMP && STEADY && KO >= 0);
   const int C = a.prob.chains_per_problem;
   const int n_other = (KO >= 0) ? KO : n_other_rt;
   const int n_cens = (KC >= 0) ? KC : n_cens_rt;
@@ -149,7 +191,7 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
   // exp and log coefficients: in VGPRs for the whole launch (8 doubles)
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
   PHF_KFETCH_V(k_log, phf_k_log, PHF_K_LOG_N);
-  chol_packed<D>(cov, L);
+  chol_packed<D>(cov, L);      // (the guarded version for every body: once per call, and chol_packed_steady gives the same doubles)
   double sc = phf_exp_fast_k(0.5 * loga, k_exp);
 
   double m1[D + 1], m2[D + 1], mll = 0.0;
@@ -206,18 +248,26 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
       star[i] = phf_fma(sc, v, th[i]);
     }
     // ---- target and accept test (PyHillFit.py:833-838) ----
-    double lik_star, prior_star, ll1_star;
-    phf_sl_log_target_shared(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature, star, k_exp, k_log,
-                             SHARE, den_off, s_den + threadIdx.x, kBlock, &lik_star, &prior_star, &ll1_star);
-    const double lt_star = lik_star + prior_star;
-    const bool acc = (D == 3) ? (bool)phf_mh_accept_u32(lt_star - lt, w_u, k_log) : log_u < lt_star - lt;
+    double lik_star, prior_star, ll1_star, lt_star;
+    bool inside = true;
+    if constexpr (STEADY) {      // a proposal outside the prior's support is rejected by the predicate, not by a -inf (phf_model.h)
+      inside = !phf_sl_log_target_sampler(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature,
+                                          kLowerClamp, star, k_exp, k_log, SHARE, den_off, s_den + threadIdx.x, kBlock, &lik_star, &prior_star,
+                                          &ll1_star, &lt_star);
+    } else {
+      phf_sl_log_target_shared(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature, star, k_exp, k_log,
+                               SHARE, den_off, s_den + threadIdx.x, kBlock, &lik_star, &prior_star, &ll1_star);
+      lt_star = lik_star + prior_star;
+    }
+    const bool acc = inside & ((D == 3) ? (bool)phf_mh_accept_u32(lt_star - lt, w_u, k_log) : log_u < lt_star - lt);
     if (acc) {
 #pragma unroll
       for (int i = 0; i < D; ++i) th[i] = star[i];
       lt = lt_star;
       ll1 = ll1_star;
+      if constexpr (STEADY) ++nacc;            // one add under the accepting lanes' mask, no 0 / 1 select
     }
-    nacc += acc ? 1u : 0u;
+    if constexpr (!STEADY) nacc += acc ? 1u : 0u;
     // ---- adaptation (PyHillFit.py:840-846; PyHillTemp.py:114-122), wave-uniform selects instead of branches ----
     double gs, gm, omg, omm;
     if constexpr (STEADY) {
@@ -251,7 +301,8 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
     uint32_t w_u_next = 0u;
     if constexpr (D == 3) w_u_next = phf_mh_draws_w3(cid, pid, t + 1u, seed_lo, seed_hi, z_next);
     else log_u_next = phf_mh_draws(D, cid, pid, t + 1u, seed_lo, seed_hi, k_log, z_next);
-    chol_packed<D>(cov, L);
+    if constexpr (STEADY && PHF_SL_STEADY_CHOL) chol_packed_steady<D>(cov, L);
+    else chol_packed<D>(cov, L);
     sc = phf_exp_fast_k(0.5 * loga, k_exp);
 #pragma unroll
     for (int i = 0; i < 3; ++i) z[i] = z_next[i];
@@ -355,7 +406,14 @@ __device__ __forceinline__ void run_block(const AdvanceArgs& a, double* s_pts, d
     if (t_to == t_end) return;
     t_from = t_to; t_to = t_end;
   }
-  if (n_other <= 5 && n_cens <= 4) {
+  // Wave-uniform: a pair with a dose of 0 (ln_conc = -inf), a NaN or a dose below e^-50 has no bound on the Hill exponentials' arguments
+  // and takes the run-time-loop body, which keeps their lower clamp (so such a pair has no straight-line body).
+  int doses_bounded = 1;
+  if (PHF_SL_STEADY_NOCLAMP && n_other <= 5 && n_cens <= 4) {
+    for (int j = 0; j < n_other + n_cens; ++j) doses_bounded &= (int)(s_pts[j] >= PHF_LN_CONC_NOCLAMP);
+    doses_bounded = __builtin_amdgcn_readfirstlane(doses_bounded);
+  }
+  if (n_other <= 5 && n_cens <= 4 && doses_bounded) {
     switch (n_other * 8 + n_cens) {                     // wave-uniform
       PHF_SHAPE_CASE(0, 1) PHF_SHAPE_CASE(0, 2) PHF_SHAPE_CASE(0, 3) PHF_SHAPE_CASE(0, 4)
       PHF_SHAPE_CASE(1, 0) PHF_SHAPE_CASE(1, 1) PHF_SHAPE_CASE(1, 2) PHF_SHAPE_CASE(1, 3) PHF_SHAPE_CASE_SHARED(1, 4, 0x8u)

@@ -6,7 +6,8 @@ kernel in a hipcc -S listing — what the vector-ALU slots of an iteration are s
     python tools/isa_itemise.py sl.s mh_advance_kernelILi2ELb0ELi2E            (produced profiles/r05/c3_valu_itemised.txt)
 
 A loop = a backward branch whose span holds no other backward branch; classes by opcode (and, for Philox, by its constants).  A region
-that a forward s_cbranch_vccz skips and that reads LDS is a rare path (the accept test's logarithm) and is listed apart, not counted."""
+that a forward s_cbranch_vccz skips and that reads LDS (the accept test's logarithm) or holds six or more selects (the guarded Cholesky
+factor of the steady bodies) is a rare path and is listed apart, not counted."""
 import collections
 import re
 import sys
@@ -76,9 +77,11 @@ def main():
             ins.append(l)
         back = []
         for i, l in enumerate(ins):
-            m = re.match(r"s_cbranch_\w+ (\.LBB\d+_\d+)|s_branch (\.LBB\d+_\d+)", l)
+            # conditional branches only: an out-of-line block behind the loop (the sample store, the temperature != 1 block of the
+            # steady bodies) returns into the body with an s_branch, which is no loop
+            m = re.match(r"s_cbranch_\w+ (\.LBB\d+_\d+)", l)
             if m:
-                lab = m.group(1) or m.group(2)
+                lab = m.group(1)
                 if lab in labels and labels[lab] <= i:
                     back.append((labels[lab], i))
         inner = [(a, b) for a, b in back if not any(a <= c and d <= b and (c, d) != (a, b) for c, d in back)]
@@ -88,13 +91,15 @@ def main():
         rare = {}
         for a, b in inner:
             # rare paths: regions a forward wave-uniform branch skips that read LDS — the accept test's logarithm (phf_mh_accept_u32 runs it
-            # only when some lane is next to its threshold, at most one iteration of a wavefront in 128): listed apart, not counted below
+            # only when some lane is next to its threshold, at most one iteration of a wavefront in 128) — or that hold six or more selects —
+            # the guarded Cholesky factor of the steady bodies (chol_packed_steady: only when some lane has a non-positive pivot):
+            # listed apart, not counted below
             skip = set()
             for i in range(a, b):
                 m = re.match(r"s_cbranch_vccz (\.LBB\d+_\d+)", ins[i])
                 if m and m.group(1) in labels and i < labels[m.group(1)] <= b:
                     region = range(i + 1, labels[m.group(1)])
-                    if any(ins[j].startswith("ds_read") for j in region):
+                    if any(ins[j].startswith("ds_read") for j in region) or sum(ins[j].startswith("v_cndmask") for j in region) >= 6:
                         skip.update(region)
             rare[a] = sorted(skip)
             body = [l for i, l in enumerate(ins[a:b + 1], a) if i not in skip]
