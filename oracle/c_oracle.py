@@ -214,16 +214,23 @@ class PackedHierPair:
         return st
 
     def advance(self, st, t_begin, t_end, thinning, adapt_start, gamma, seed=25, chain_id=0, problem_id=0,
-                star_replay=None, u_replay=None):
+                star_replay=None, u_replay=None, trace=False):
+        """trace=True: returns (rows, trace), trace[t - t_begin - 1] = (log-target of iteration t's proposal, 1.0 if accepted else 0.0,
+        1.0 if the proposal lies outside the support else 0.0)"""
         rows = t_end // thinning - t_begin // thinning
         out = np.zeros((rows, self.dim + 1))
         run = Run(t_begin, t_end, thinning, 0, adapt_start, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, chain_id,
                   problem_id, _p(gamma))
         sr = np.ascontiguousarray(star_replay, dtype=np.float64) if star_replay is not None else None
         ur = np.ascontiguousarray(u_replay, dtype=np.float64) if u_replay is not None else None
-        lib().phfo_hier_advance(C.byref(self.pb), C.byref(run), _p(st), _p(out), _p(sr) if sr is not None else None,
-                                _p(ur) if ur is not None else None)
-        return out
+        if not trace:
+            lib().phfo_hier_advance(C.byref(self.pb), C.byref(run), _p(st), _p(out), _p(sr) if sr is not None else None,
+                                    _p(ur) if ur is not None else None)
+            return out
+        tr = np.zeros((t_end - t_begin, 3))
+        lib().phfo_hier_advance_traced(C.byref(self.pb), C.byref(run), _p(st), _p(out), _p(sr) if sr is not None else None,
+                                       _p(ur) if ur is not None else None, _p(tr))
+        return out, tr
 
 
 def hier_state_covariance(st, dim):

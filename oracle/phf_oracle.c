@@ -201,9 +201,11 @@ void phfo_hier_init_state(const phfo_hier_problem* pb, double cov_scale, const d
 
 /* The hierarchical loop (PyHillFit.py:484-511).  The covariance recursion cov <- (1-g) cov + g v v' (:498-499) is
  * carried on the factors cov = L diag(d) L' (L unit lower): d scales by 1-g, then the rank-one update of Gill, Golub, Murray &
- * Saunders (1974, method C1) with weight g and vector v, column by column. */
-void phfo_hier_advance(const phfo_hier_problem* pb, const phfo_run* run, double* st, double* out_rows,
-                       const double* star_replay, const double* u_replay) {
+ * Saunders (1974, method C1) with weight g and vector v, column by column.
+ * trace (tests, may be NULL: nothing else changes): three doubles per iteration — the proposal's log-target, the accept decision, and
+ * whether the proposal lies outside the support. */
+void phfo_hier_advance_traced(const phfo_hier_problem* pb, const phfo_run* run, double* st, double* out_rows,
+                              const double* star_replay, const double* u_replay, double* trace) {
   const int d = 5 + 2 * pb->n_expts;
   const int ntri = d * (d + 1) / 2;
   double* th = st; double* lt = st + d; double* mean = st + d + 1; double* L = mean + d;
@@ -232,6 +234,10 @@ void phfo_hier_advance(const phfo_hier_problem* pb, const phfo_run* run, double*
     const int acc = log_u < lt_star - *lt;                                 /* :487-492 */
     if (acc) { for (int i = 0; i < d; ++i) th[i] = star[i]; *lt = lt_star; }
     *nacc += (double)acc;
+    if (trace) {
+      double* tr = trace + 3 * (t - run->t_begin - 1);
+      tr[0] = lt_star; tr[1] = (double)acc; tr[2] = (double)(phf_hier_out_of_support(pb->n_expts, star, 1, &pb->prior) != 0);
+    }
     if (t > run->adapt_start) {                                            /* :495-501 */
       const double g = run->gamma[t - run->adapt_start];
       const double omg = 1.0 - g;
@@ -262,6 +268,11 @@ void phfo_hier_advance(const phfo_hier_problem* pb, const phfo_run* run, double*
       ++row;
     }
   }
+}
+
+void phfo_hier_advance(const phfo_hier_problem* pb, const phfo_run* run, double* st, double* out_rows,
+                       const double* star_replay, const double* u_replay) {
+  phfo_hier_advance_traced(pb, run, st, out_rows, star_replay, u_replay, NULL);
 }
 
 /* ---------------------------------------------------------------- leaf-function probes (tests) */

@@ -21,27 +21,36 @@ def _bits_equal(a, b):
     return np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
+# what a chain at an edge state feeds the elementary functions: +NaN, a NaN with the sign bit set, subnormals, zeros and infinities of both
+# signs; and, for log, rcp and sqrt, negative normal numbers.  Every table index is masked or clamped for any bit pattern
+SPECIALS = np.array([0x7ff8000000000000, 0xfff8000000000000, 0x0000000000000001, 0x8000000000000001, 0x000fffffffffffff, 0x800fffffffffffff,
+                     0x0000000000000000, 0x8000000000000000, 0x7ff0000000000000, 0xfff0000000000000], dtype=np.uint64).view(np.float64)
+NEGATIVE_NORMALS = np.array([-1.0, -2.5, -2.0 ** -1022, -1e-300, -1e300, -1.7976931348623157e308])
+
+
 def test_isa_elementary_functions_bit_identical_to_the_hipcc_build(gpu):
     from pyhillfit_amd.sampler import debug_isa, debug_math
     rng = np.random.default_rng(7)
     n = 200000
+    assert np.isnan(SPECIALS[:2]).all() and np.signbit(SPECIALS[1]) and not np.signbit(SPECIALS[0])
     # exp: the whole clamped range and beyond, zeros, infinities
-    x = np.concatenate([rng.uniform(-760, 720, n), rng.normal(0, 3, n), [0.0, -0.0, 709.9, 710.0, 711.0, -745.9, -746.0, -800.0, np.inf, -np.inf, 1e-300]])
+    x = np.concatenate([rng.uniform(-760, 720, n), rng.normal(0, 3, n), [0.0, -0.0, 709.9, 710.0, 711.0, -745.9, -746.0, -800.0, np.inf, -np.inf, 1e-300], SPECIALS])
     assert _bits_equal(debug_isa(0, x, gpu), debug_math(9, x, gpu)), "phf_exp_fast_k"
-    xc = x[x <= 709.0]
+    xc = np.concatenate([x[x <= 709.0], SPECIALS[:2]])                          # (the capped form is phf_exp_fast_k wherever the cap is idle: not at +inf)
     assert _bits_equal(debug_isa(1, xc, gpu), debug_math(9, xc, gpu)), "phf_exp_capped_k"
     # log: positive normal numbers over the whole exponent range, near 1, powers of two
     xp = np.concatenate([np.exp(rng.uniform(-700, 700, n)), 1.0 + rng.normal(0, 1e-3, n), 2.0 ** rng.integers(-1000, 1000, 1000), [1.0, 2.0 ** -1022, 1.7976931348623157e308]])
-    assert _bits_equal(debug_isa(2, xp, gpu), debug_math(10, xp, gpu)), "phf_log_pos_k"
-    xl = np.concatenate([xp, [0.0, -0.0, -1.0, 1e-310, 2.0 ** -1023, -np.inf]])
+    xn = np.concatenate([xp, SPECIALS[:1], [np.inf]])                           # (phf_log_fast_k is phf_log_pos_k from 2^-1022 up, +NaN and +inf included)
+    assert _bits_equal(debug_isa(2, xn, gpu), debug_math(10, xn, gpu)), "phf_log_pos_k"
+    xl = np.concatenate([xp, [0.0, -0.0, -1.0, 1e-310, 2.0 ** -1023, -np.inf], SPECIALS, NEGATIVE_NORMALS])
     assert _bits_equal(debug_isa(3, xl, gpu), debug_math(10, xl, gpu)), "phf_log_fast_k"
     # erfc table: the table's range, the cut, beyond it, negatives (clamped index: any value is safe)
-    y = np.concatenate([rng.uniform(0, 6.5, n), rng.uniform(-1, 40, n), [0.0, 5.999999, 6.0, 6.000001, 1e5, 1e300]])
+    y = np.concatenate([rng.uniform(0, 6.5, n), rng.uniform(-1, 40, n), [0.0, 5.999999, 6.0, 6.000001, 1e5, 1e300], SPECIALS])
     assert _bits_equal(debug_isa(4, y, gpu), debug_math(19, y, gpu)), "phf_erfc_tab"
     # reciprocal, square root
-    xr = np.concatenate([np.exp(rng.uniform(-400, 400, n)) * rng.choice([-1.0, 1.0], n), [1.0, -1.0, 3.0]])
+    xr = np.concatenate([np.exp(rng.uniform(-400, 400, n)) * rng.choice([-1.0, 1.0], n), [1.0, -1.0, 3.0], SPECIALS, NEGATIVE_NORMALS])
     assert _bits_equal(debug_isa(5, xr, gpu), debug_math(12, xr, gpu)), "phf_rcp"
-    xs = np.concatenate([np.exp(rng.uniform(-400, 400, n)), [0.0, -0.0, -1.0, 4.0]])
+    xs = np.concatenate([np.exp(rng.uniform(-400, 400, n)), [0.0, -0.0, -1.0, 4.0], SPECIALS, NEGATIVE_NORMALS])
     assert _bits_equal(debug_isa(6, xs, gpu), debug_math(15, xs, gpu)), "phf_sqrt_nonneg"
     # normals and the accept uniform's logarithm from 32-bit words
     w = np.concatenate([rng.integers(0, 2 ** 32, n, dtype=np.uint64), [0, 1, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1]]).astype(np.uint32)

@@ -59,6 +59,26 @@ def test_device_math_bit_identical_to_host_build(gpu):
     for fn, (name, x) in cases.items():
         got, want = debug_math(fn, x, gpu), co.vec(name, x)
         assert np.array_equal(got, want, equal_nan=True), "%s: %d mismatches" % (name, int((got != want).sum()))
+    # edge arguments on every one of them: +NaN, a NaN with the sign bit set, subnormals, zeros and infinities of both signs, negative normal
+    # numbers — bit for bit (a zero's sign included); a NaN compares as "is NaN" (its payload and sign are the hardware's)
+    from test_gpu_isa import NEGATIVE_NORMALS, SPECIALS
+    edge = np.concatenate([SPECIALS, NEGATIVE_NORMALS])
+
+    def same_bits_nan_as_nan(got, want):
+        nan = np.isnan(want)
+        return np.array_equal(np.isnan(got), nan) and np.array_equal(got[~nan].view(np.uint64), want[~nan].view(np.uint64))
+    for fn, (name, _) in cases.items():
+        got, want = debug_math(fn, edge, gpu), co.vec(name, edge)
+        assert same_bits_nan_as_nan(got, want), (name, edge[got.view(np.uint64) != want.view(np.uint64)].tolist(), got.tolist(), want.tolist())
+    # phf_rcp and phf_sqrt_nonneg are the host's 1 / x and sqrt between 2^-600 and 2^600; outside (phf_math.h: zeros, subnormals, infinities — operands
+    # a live chain never has) the device may answer NaN where the host has an infinity or a zero, and agrees otherwise
+    with np.errstate(all="ignore"):
+        for fn, want, name in ((12, 1.0 / edge, "phf_rcp"), (15, np.where(edge > 0, np.sqrt(np.abs(edge)), 0.0), "phf_sqrt_nonneg")):
+            got = debug_math(fn, edge, gpu)
+            inside = np.isfinite(edge) & (np.abs(edge) >= 2.0 ** -600) & (np.abs(edge) <= 2.0 ** 600)
+            assert inside.sum() == 2 and same_bits_nan_as_nan(got[inside], want[inside]), (name, got.tolist())
+            ok = (got.view(np.uint64) == want.view(np.uint64)) | np.isnan(got)
+            assert ok.all(), (name, edge[~ok].tolist(), got[~ok].tolist(), want[~ok].tolist())
     x = np.concatenate([np.exp(rng.uniform(-700, 700, n)), -np.exp(rng.uniform(-5, 5, n))])
     assert np.array_equal(debug_math(6, x, gpu), 1.0 / x)                      # IEEE division
     # the MH loops' own division / square root: hipcc's iterations without the exponent-range handling (phf_math.h) must still
