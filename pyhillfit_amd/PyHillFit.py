@@ -258,7 +258,9 @@ def load_single_level_pairs(pairs):
 def run_single_level(pairs, args, device, rank=0, world=1):
     """All pairs of this rank at once — replaces python/PyHillFit.py:645-971 run per pair."""
     import torch
+    from . import analyses as an
     from .sampler import SingleLevelSampler
+    from .waic import Points
     model, temperature = args.model, 1                                 # PyHillFit.py:57
     t_begin = time.time()
     loaded = load_single_level_pairs(pairs)
@@ -282,9 +284,9 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     assert total_iterations % thinning == 0                            # PyHillFit.py:805
     packed = dr.PackedPoints([(c, y) for _, _, c, y in loaded])
     Q, C = len(loaded), args.num_chains
+    problem_ids = [p[4] for p in pairs_with_ids(pairs, loaded)]
     s = SingleLevelSampler(packed, model, list(range(Q)), [1.0] * Q, C, thinning=thinning, seed=args.seed,
-                           adapt_start=1000 * dr.num_params, problem_ids=[p[4] for p in pairs_with_ids(pairs, loaded)],
-                           device=device)
+                           adapt_start=1000 * dr.num_params, problem_ids=problem_ids, device=device)
     s.init(np.array(theta0), cov_identity=False, cov_scale=0.05)       # PyHillFit.py:748-751
     saved_iterations = total_iterations // thinning + 1                # :810
     burn = saved_iterations // args.burn_in_fraction                   # :862
@@ -298,66 +300,13 @@ def run_single_level(pairs, args, device, rank=0, world=1):
             raise SystemExit("--save-all-chains needs {:.1f} GB of device memory for {} pairs x {} chains x {} saved rows, {:.1f} GB are free: "
                              "select fewer pairs (--drugs/--channels), fewer chains or a larger thinning".format(need / 1e9, Q, C, saved_iterations, free / 1e9))
     d = s.d
-    diag = None
-    if args.diagnostics:
-        from . import diagnostics as dg
-        diag_rows = saved_iterations - burn
-        dg.check_memory(dg.workspace_bytes(Q, d + 1, C, diag_rows, args.diagnostic_lags), device)
-        diag = dg.ChainDiagnostics(Q, C, d + 1, diag_rows, args.diagnostic_lags, device)
-        if burn == 0:
-            diag.accumulate(s.row0.unsqueeze(0).contiguous())
-    bmeans = None
-    if getattr(args, "diagnostic_batch_means", False):
-        from . import batch_means as bm
-        bm.check_memory(bm.workspace_bytes(Q, d + 1, C, saved_iterations - burn), device)
-        bmeans = bm.BatchMeans(Q, C, d + 1, saved_iterations - burn, device)
-        if burn == 0:
-            bmeans.accumulate(s.row0.unsqueeze(0).contiguous())
-    waic = None
-    if getattr(args, "waic", False):
-        from . import waic as wc
-        wpts = wc.Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))
-        wc.check_memory(wc.workspace_bytes(Q, wpts.stride, C, saved_iterations - burn), device)
-        waic = wc.PointwiseWAIC(wpts, model, Q, C, saved_iterations - burn, device)
-        if burn == 0:
-            waic.accumulate(s.row0.unsqueeze(0).contiguous())
-    psis = None
-    if getattr(args, "loo", False):
-        from . import loo as lo
-        from . import waic as wc
-        lpts = wc.Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))
-        lo.check_memory(lo.workspace_bytes(Q, lpts.stride, C, saved_iterations - burn, args.loo_tail_per_chain), device)
-        psis = lo.PointwiseLOO(lpts, model, Q, C, saved_iterations - burn, device, args.loo_tail_per_chain)
-        if burn == 0:
-            psis.accumulate(s.row0.unsqueeze(0).contiguous())
-    quant, doses = None, None
-    if getattr(args, "quantiles", False):
-        from . import quantiles as qn
-        G = getattr(args, "curve_bands", 0)
-        doses = [qn.curve_doses(concs, G) for _, _, concs, _ in loaded] if G else None
-        qn.check_memory(qn.workspace_bytes(Q, d + 1, G, args.quantile_bins), device)
-        quant = qn.PosteriorQuantiles(Q, C, d + 1, saved_iterations - burn, args.quantile_probs, args.quantile_bins, device,
-                                      curve_ln_doses=np.log(np.array(doses)) if G else None, model=model)
-        if burn == 0:
-            quant.accumulate(s.row0.unsqueeze(0).contiguous())
-    ppc = None
-    if getattr(args, "ppc", False):
-        from . import ppc as pp
-        from . import waic as wc
-        ppts = wc.Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))
-        pp.check_memory(pp.workspace_bytes(Q, ppts.stride, C, saved_iterations - burn), device)
-        ppc = pp.PosteriorPredictiveCheck(ppts, model, Q, C, saved_iterations - burn, args.seed,
-                                          [p[4] for p in pairs_with_ids(pairs, loaded)], 0, device)
-        if burn == 0:
-            ppc.accumulate(s.row0.unsqueeze(0).contiguous())
-    sens = None
-    if getattr(args, "sensitivity", False):
-        from . import sensitivity as sn
-        sn.check_memory(sn.workspace_bytes(Q, d, C, saved_iterations - burn, args.sensitivity_bins), device)
-        sens = sn.PowerScaling(s.points, model, Q, C, d, saved_iterations - burn, args.sensitivity_delta, args.sensitivity_bins, device,
-                               threshold=args.sensitivity_threshold)
-        if burn == 0:
-            sens.accumulate(s.row0.unsqueeze(0).contiguous())
+    columns = dr.file_labels + ["log-target"]
+    kinds = an.fit_analyses(args)
+    aset = an.AnalysisSet(kinds, an.Run(
+        args=args, kind=model, Q=Q, C=C, cols=d + 1, columns=columns, saved=saved_iterations, burn=burn, device=device,
+        sampler_points=s.points, concs=[concs for _, _, concs, _ in loaded], seed=args.seed, problem_ids=problem_ids, prior=None, de=None,
+        make_points=lambda: Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))))
+    aset.feed_start(s.row0)
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
             chainio.host_buffer((saved_iterations, Q, d + 1, 1)))   # pinned: chain 0 leaves the GPU asynchronously
     kept[0] = s.row0 if keep_all else s.row0[:, :, :1].cpu()
@@ -370,21 +319,7 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         k = min(seg, total_iterations - done)
         nr = k // thinning
         rows = s.advance(k, out=buf[:nr])
-        first = max(0, burn - r)                                       # saved rows before `burn` are the burn-in
-        if diag is not None and first < nr:
-            diag.accumulate(rows[first:])
-        if bmeans is not None and first < nr:
-            bmeans.accumulate(rows[first:])
-        if waic is not None and first < nr:
-            waic.accumulate(rows[first:])
-        if psis is not None and first < nr:
-            psis.accumulate(rows[first:])
-        if quant is not None and first < nr:
-            quant.accumulate(rows[first:])
-        if ppc is not None and first < nr:
-            ppc.accumulate(rows[first:])
-        if sens is not None and first < nr:
-            sens.accumulate(rows[first:])
+        aset.feed(rows, r, nr)                                         # saved rows before `burn` are the burn-in
         # stream-ordered and asynchronous: the next segment is queued behind this copy while the host moves on (a blocking copy
         # here left the GPU idle for the gather + transfer + launch latency of every segment)
         kept[r:r + nr].copy_(rows if keep_all else rows[:, :, :, :1], non_blocking=True)
@@ -394,23 +329,7 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     mean, var, n_mom = s.posterior_moments()
     mean, var = mean.cpu().numpy(), var.cpu().numpy()
     acc = s.acceptance().cpu().numpy()
-    diag_res = diag.result() if diag is not None else None
-    bm_res = bmeans.result() if bmeans is not None else None
-    if bmeans is not None:
-        bmeans.free()
-    waic_res = waic.result() if waic is not None else None
-    loo_res = psis.result() if psis is not None else None
-    if psis is not None:
-        psis.free()
-    quant_res = quant.result() if quant is not None else None
-    if quant is not None:
-        quant.free()
-    ppc_res = ppc.result() if ppc is not None else None
-    if ppc is not None:
-        ppc.free()
-    sens_res = sens.result() if sens is not None else None
-    if sens is not None:
-        sens.free()
+    aset.finish()
     summaries = []
     for q, (d_clean, c_clean, chain_file) in enumerate(files):
         chain0 = kept[:, q, :, 0].cpu().numpy()
@@ -421,48 +340,18 @@ def run_single_level(pairs, args, device, rank=0, world=1):
         pooled_sd = np.sqrt(var[:, q].mean(axis=1) + mean[:, q].var(axis=1))
         summ = {"drug": d_clean, "channel": c_clean, "model": model, "chains": C, "iterations": total_iterations,
                 "thinning": thinning, "saved_rows_after_burn_in": int(saved_iterations - burn),
-                "columns": dr.file_labels + ["log-target"], "pooled_mean": pooled_mean.tolist(), "pooled_sd": pooled_sd.tolist(),
+                "columns": columns, "pooled_mean": pooled_mean.tolist(), "pooled_sd": pooled_sd.tolist(),
                 "per_chain_mean_sd": mean[:, q].std(axis=1).tolist(), "acceptance": float(acc[q].mean()),
                 "start_point": np.asarray(theta0[q]).tolist(), "seed": args.seed,
                 "mh_samples_per_second": Q * C * total_iterations / elapsed}
-        if diag_res is not None:
-            summ["diagnostics"] = dg.json_record(diag_res, q, args.diagnostic_lags, saved_iterations - burn, C)
-            if bm_res is not None:
-                summ["diagnostics"]["batch_means"] = bm.json_record(bm_res, q)
-        if waic_res is not None:
-            summ["waic"] = wc.json_record(waic_res[q], wpts, q)
-        if loo_res is not None:
-            summ["loo"] = lo.json_record(loo_res[q], lpts, q, psis.M, psis.k)
-        if quant_res is not None:
-            summ["quantiles"] = qn.json_record(quant_res, q, dr.file_labels + ["log-target"], args.quantile_bins)
-            if doses is not None:
-                summ["curve_band"] = qn.curve_band_record(quant_res, q, doses[q])
-        if ppc_res is not None:
-            summ["ppc"] = pp.json_record(ppc_res[q], ppts, q)
-        if sens_res is not None:
-            summ["sensitivity"] = sn.json_record(sens_res, q, dr.file_labels)
+        aset.record(summ, q)
         with open(chain_file[:-4] + "_summary.json", "w") as f:
             json.dump(summ, f, indent=1)
         summaries.append(summ)
         print("\n\n{} + {} complete!\n\n".format(d_clean, c_clean))      # PyHillFit.py:970
     writers.close()
-    if diag_res is not None:
-        print(dg.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], diag_res["rhat"], diag_res["ess"]))
-    if bm_res is not None:
-        print(bm.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], diag_res["ess"], bm_res["ess"], bm_res["tau"], thinning))
-    if waic_res is not None:
-        print(wc.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], waic_res))
-    if loo_res is not None:
-        print(lo.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], loo_res))
-    if quant_res is not None:
-        n = d + 1
-        print(qn.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files],
-                             [(quant_res["bin_width"][q, :n], quant_res["min"][q, :n], quant_res["max"][q, :n], quant_res["non_finite"][q, :n])
-                              for q in range(len(files))]))
-    if ppc_res is not None:
-        print(pp.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], ppc_res))
-    if sens_res is not None:
-        print(sn.report_line(rank, ["{} + {}".format(f[0], f[1]) for f in files], [sn.part_of(sens_res, q) for q in range(len(files))]))
+    for line in an.report(kinds, [aset], rank, ["{} + {}".format(f[0], f[1]) for f in files], args):
+        print(line)
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, Q * C, total_iterations, time.time() - start - elapsed))
     return summaries

@@ -190,6 +190,8 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     Every rank writes the chain files of its own units; rank 0 gathers the per-unit expectations, writes one
     thermodynamic_integration.json per pair and ONE run summary, and returns the per-rung records (other ranks: [])."""
     import torch
+    from . import analyses as an
+    from . import diagnostics as dg
     from .sampler import SingleLevelSampler
     model = args.model
     d = dr.num_params
@@ -226,8 +228,6 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
     if args.diagnostic_batch_means:   # per unit and column: batch_means.FIELDS; they ride on the same gather
         from . import batch_means as bm
         unit_rows = np.concatenate([unit_rows, np.zeros((len(mine), len(bm.FIELDS) * (d + 1)))], axis=1)
-    # the rows the fused <log L(t=1)> counts: saved rows with t > moments_after, i.e. row index >= max(burn, 1)
-    first_kept = max(burn, 1)
     mcmc_time = 0.0
     if len(mine):
         packed = dr.PackedPoints([(loaded[ip][2], loaded[ip][3]) for ip in my_pairs])
@@ -247,24 +247,11 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
         writers = chainio.WriterPool(args.write_workers if args.write_workers is not None else chainio.default_write_workers(world))
         seg = max(thinning, args.segment - args.segment % thinning)
         buf = torch.empty((seg // thinning, Q, d + 1, C), dtype=torch.float64, device=device)
-        diag = None
-        if args.diagnostics:
-            from . import diagnostics as dg
-            dg.check_memory(dg.workspace_bytes(Q, d + 1, C, num_saved - burn, args.diagnostic_lags), device)
-            diag = dg.ChainDiagnostics(Q, C, d + 1, num_saved - burn, args.diagnostic_lags, device)
-            if burn == 0:
-                diag.accumulate(s.row0.unsqueeze(0).contiguous())
-        bmeans = None
-        if args.diagnostic_batch_means:
-            bm.check_memory(bm.workspace_bytes(Q, d + 1, C, num_saved - burn), device)
-            bmeans = bm.BatchMeans(Q, C, d + 1, num_saved - burn, device)
-            if burn == 0:
-                bmeans.accumulate(s.row0.unsqueeze(0).contiguous())
-        sst = None
-        if args.stepping_stone:
-            delta = ss.deltas(temperatures)
-            ss.check_memory(ss.workspace_bytes(Q, C, num_saved - first_kept), device)
-            sst = ss.SteppingStone(s.points, model, pair_index, [float(delta[int(u) % R]) for u in mine], C, num_saved - first_kept, device)
+        aset = an.AnalysisSet(an.tempered_analyses(args), an.Run(
+            args=args, kind=model, Q=Q, C=C, cols=d + 1, saved=num_saved, burn=burn, device=device, sampler_points=s.points,
+            pair_index=pair_index, rung_index=[int(u) % R for u in mine], temperatures=temperatures, num_pairs=len(my_pairs), swap=swap))
+        aset.feed_start(s.row0)
+        diag, bmeans, sst = aset.of(an.Diagnostics), aset.of(an.BatchMeans), aset.of(an.SteppingStone)
         rx = rxm.ReplicaExchange(s, R) if swap > 0 else None      # the units are whole pairs, pair-major, rungs in order
         done, r = 0, 1
         start = time.time()
@@ -272,14 +259,7 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
             k = min(seg, total_iterations - done)
             nr = k // thinning
             rows = s.advance(k, out=buf[:nr]) if rx is None else rx.advance(k, every=swap, out=buf[:nr])
-            first = max(0, burn - r)                                    # saved rows before `burn` are the burn-in
-            if diag is not None and first < nr:
-                diag.accumulate(rows[first:])
-            if bmeans is not None and first < nr:
-                bmeans.accumulate(rows[first:])
-            first = max(0, first_kept - r)
-            if sst is not None and first < nr:
-                sst.accumulate(rows[first:])
+            aset.feed(rows, r, nr)                                      # saved rows before `burn` are the burn-in
             kept[r:r + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # stream-ordered; the next segment is queued behind it at once
             done += k; r += nr
         torch.cuda.synchronize(device)
@@ -288,25 +268,21 @@ def run_tempered(pairs, temperatures, args, device, rank=0, world=1):
         mean, var, _ = s.posterior_moments()
         mean = mean.cpu().numpy()
         ll1 = s.mean_log_likelihood_t1().cpu().numpy()            # [Q][C]  E_rung[log L(theta; t=1)], fused into the sampler
+        aset.finish()
+        unit_names = ["{} + {} at t = {:g}".format(loaded[int(u) // R][0], loaded[int(u) // R][1], temperatures[int(u) % R]) for u in mine]
         if diag is not None:
-            res = diag.result()
+            res = diag.res
             unit_rows[:, width:ss_first] = np.concatenate([res["rhat"], res["ess"], res["mcse_mean"], res["lag_limit_reached"].astype(np.float64)], axis=1)
-            print(dg.report_line(rank, ["{} + {} at t = {:g}".format(loaded[int(u) // R][0], loaded[int(u) // R][1], temperatures[int(u) % R])
-                                        for u in mine], res["rhat"], res["ess"]))
+            print(dg.report_line(rank, unit_names, res["rhat"], res["ess"]))
         if bmeans is not None:
-            bres = bmeans.result()
-            bmeans.free()
+            bres = bmeans.res
             unit_rows[:, bm_first:] = np.concatenate([np.asarray(bres[k], dtype=np.float64) for k in bm.FIELDS], axis=1)
-            print(bm.report_line(rank, ["{} + {} at t = {:g}".format(loaded[int(u) // R][0], loaded[int(u) // R][1], temperatures[int(u) % R])
-                                        for u in mine], res["ess"], bres["ess"], bres["tau"], thinning))
+            print(bm.report_line(rank, unit_names, res["ess"], bres["ess"], bres["tau"], thinning))
         if sst is not None:
-            unit_rows[:, ss_first:ss_first + len(ss.OUT)] = sst.reduced()
+            unit_rows[:, ss_first:ss_first + len(ss.OUT)] = sst.res
         if rx is not None:
-            se_joint = rxm.joint_se(sst, len(my_pairs), R) if sst is not None else None
-            unit_rows[:, rx_first:bm_first] = rxm.unit_columns(rx.statistics(), rx.rounds, len(my_pairs), R, se_joint,
+            unit_rows[:, rx_first:bm_first] = rxm.unit_columns(rx.statistics(), rx.rounds, len(my_pairs), R, sst.se_joint if sst is not None else None,
                                                        rxm.replica_set_ti_se(ll1, temperatures, len(my_pairs)))
-        if sst is not None:
-            sst.free()
         for q, u in enumerate(mine):
             ip, ir = int(u) // R, int(u) % R
             drug, channel = loaded[ip][0], loaded[ip][1]

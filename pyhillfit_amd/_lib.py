@@ -2,6 +2,7 @@
 
 There is NO CPU fallback: if the HIP library is missing or a call fails, this raises."""
 import ctypes as C
+import math
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -181,3 +182,9 @@ PHF_ERR_UNSUPPORTED = -3          # include/pyhillfit_amd.h
 def check(rc, what=""):
     if rc != 0:
         raise PhfError("%s failed (%d): %s" % (what or "pyhillfit_amd call", rc, load().phf_last_error().decode()))
+
+
+def _num(v):
+    """a number for the JSON records: NaN and the infinities -> None (null)"""
+    v = float(v)
+    return v if math.isfinite(v) else None

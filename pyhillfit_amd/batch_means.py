@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
 METHOD = ("batch means on a dyadic ladder of batch sizes (Flyvbjerg & Petersen 1989) over split half-chains: sigma2 at the first rung "
@@ -155,11 +156,6 @@ def diagnose(chains, device="cuda"):
     return {k: v[0] for k, v in d.result().items()}
 
 
-def _num(v):
-    v = float(v)
-    return None if not np.isfinite(v) else v
-
-
 def json_record(res, q, de_coupled=False):
     """the "batch_means" object inside the command lines' "diagnostics" object of problem q (NaN -> null)"""
     rec = {}
@@ -189,8 +185,3 @@ def report_line(rank, names, ess_geyer, ess_ladder, tau, thinning):
                else "no tau determined")
     return "batch means [rank {}]: {} of {} with an ESS determined by neither estimator on some column; {}".format(
         rank, neither, len(names), largest)
-
-
-def check_memory(nbytes, device):
-    from . import diagnostics as dg
-    dg.check_memory(nbytes, device, "--diagnostic-batch-means")

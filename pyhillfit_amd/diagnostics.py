@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
 DEFAULT_LAGS = 256
@@ -143,11 +144,6 @@ def diagnose(chains, lags=DEFAULT_LAGS, device="cuda"):
     return {k: v[0] for k, v in d.result().items()}
 
 
-def _num(v):
-    v = float(v)
-    return None if not np.isfinite(v) else v
-
-
 def json_record(res, q, lags, total_rows, chains, columns=None):
     """the command lines' "diagnostics" object of problem q (NaN -> null)"""
     rec = {"rhat": [_num(v) for v in res["rhat"][q]], "ess": [_num(v) for v in res["ess"][q]],
@@ -169,11 +165,3 @@ def report_line(rank, names, rhat, ess):
     w = int(np.argmax(worst))
     return ("diagnostics [rank {}]: {} of {} with R-hat > {} on some column, {} with an ESS not determined; worst: {} (R-hat {:.4f})"
             .format(rank, bad, len(names), RHAT_THRESHOLD, undetermined, names[w], float(worst[w])))
-
-
-def check_memory(nbytes, device, what="--diagnostics"):
-    """refuse to start when the workspace would take more than 80 % of the free device memory (as --save-all-chains does)"""
-    free = torch.cuda.mem_get_info(device)[0]
-    if nbytes > 0.8 * free:
-        raise SystemExit("{} needs {:.1f} GB of device memory for its workspace, {:.1f} GB are free: select fewer pairs, fewer chains "
-                         "or a smaller --diagnostic-lags".format(what, nbytes / 1e9, free / 1e9))

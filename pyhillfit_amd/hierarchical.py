@@ -13,9 +13,10 @@ import numpy as np
 import torch
 
 from . import _lib, bestfit, chainio
-from . import diagnostics as dg
+from . import analyses as an
 from . import doseresponse as dr
 from .sampler import _ptr, _stream_ptr, gamma_table, raise_if_drained
+from .waic import Points
 
 # ---- Gamma hyper-priors: python/PyHillFit.py:301,340-364 (numbers from Elkins et al., as in the reference) ----------
 ELKINS_HILL_ALPHAS = np.array([1.188, 1.744, 1.530, 0.930, 0.605, 1.325, 1.179, 0.979, 1.790, 1.708, 1.586, 1.469,
@@ -499,7 +500,7 @@ first_iteration = bestfit.hierarchical_first_iteration
 
 def cdf_chains(args, num_chains):
     """how many chains of every pair feed the posterior-predictive curves: --cdf-chains, default all"""
-    n = getattr(args, "cdf_chains", 0)
+    n = args.cdf_chains
     return num_chains if n <= 0 else min(n, num_chains)
 
 
@@ -511,7 +512,9 @@ def hierarchical_columns(ne):
 
 def run_hierarchical(pairs, args, device, rank=0, world=1):
     """All pairs of this rank — replaces python/PyHillFit.py:213-642 run per pair."""
+    from .PyHillFit import experiments_and_labels
     t_begin = time.time()
+    kinds = an.fit_analyses(args)
     shapes, scales, locs = prior_params()
     prior = make_prior(shapes, scales, locs)
     groups, loaded = {}, []
@@ -533,7 +536,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         loaded.append((drug, channel, experiments, all_pairs.index((drug, channel)), fitted_all))
     # one persistent grid for the groups the gfx950 code object has kernels for (FusedSamplers) — when the run's chains give every SIMD a
     # one-lane wavefront (below that the groups run the two-lane kernels, whose wall time is the latency of one wavefront-iteration)
-    mode = getattr(args, "fused_launch", "auto")
+    mode = args.fused_launch
     one_lane = -(-args.num_chains // 64) * len(loaded) >= simd_count()
     use_fused = mode == "on" or (mode == "auto" and one_lane)
     for item in loaded:
@@ -544,13 +547,14 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
     burn = saved_iterations // 4                                       # :472
     rng = np.random.RandomState(args.seed)
     rng_pred = np.random.RandomState(1)                                # construct_hierarchical_cdfs.py:12-13
-    writers = chainio.WriterPool(getattr(args, "write_workers", 0))    # one pool for the start-point fits and the file formatting
-    chain_streams = chainio.StreamWriters(getattr(args, "write_workers", 0))   # the chain files, written segment by segment
+    writers = chainio.WriterPool(args.write_workers)                   # one pool for the start-point fits and the file formatting
+    chain_streams = chainio.StreamWriters(args.write_workers)   # the chain files, written segment by segment
     # one sampler and one HIP stream per Ne group: the groups are independent, their launches overlap on the GPU
-    if getattr(args, "loo", False):                                    # every group's PSIS-LOO workspace together, before any is made
+    if args.loo:                                                       # every group's PSIS-LOO workspace together, before any is made
         from . import loo as lo
-        lo.check_memory(sum(lo.workspace_bytes(len(m), max(sum(len(x) for x in it[2]) for it in m), args.num_chains,
-                                               saved_iterations - burn, args.loo_tail_per_chain) for m in groups.values()), device)
+        an.check_memory(sum(lo.workspace_bytes(len(m), max(sum(len(x) for x in it[2]) for it in m), args.num_chains,
+                                               saved_iterations - burn, args.loo_tail_per_chain) for m in groups.values()),
+                        device, an.Loo.what, an.Loo.hint)
     runs = []
     ordered = sorted(groups.items(), reverse=True)
     # all start points first, in one sweep over the worker pool (the file-writer processes start after it)
@@ -566,7 +570,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         s.init(theta0, cov_scale=0.01)                                 # :431
         s.enable_moments(after_iteration=max(burn * thinning - 1, 0))
         s.reserve(total_iterations)
-        if getattr(args, "de_every", 0):                               # differential-evolution moves between the chains of each pair
+        if args.de_every:                                              # differential-evolution moves between the chains of each pair
             s.enable_de_moves(args.de_every, args.de_population, args.de_gamma, args.de_jump_every)
         kept = chainio.host_buffer((saved_iterations, Q, d + 1))   # pinned: the per-segment copies are asynchronous
         kept[0] = s.row0[:, :, 0].cpu()
@@ -577,89 +581,16 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             chain_streams.create(paths[5], chainio.HIERARCHICAL_HEADER, kept[0:1, q].numpy())
         seg = max(thinning, args.segment - args.segment % thinning)
         buf = torch.empty((seg // thinning, Q, d + 1, C), dtype=torch.float64, device=device)
-        curves = None
-        if getattr(args, "predictive_cdfs", False):                    # construct_hierarchical_cdfs.py fused into the run
-            from .predictive import PredictiveCurves
-            curves = PredictiveCurves(Q, device)
-            if burn == 0:
-                curves.accumulate(s.row0.unsqueeze(0).contiguous(), cdf_chains(args, C))
-        diag = None
-        if getattr(args, "diagnostics", False):                        # split-R-hat / ESS / MCSE over all chains, accumulated like the curves
-            dg.check_memory(dg.workspace_bytes(Q, d + 1, C, saved_iterations - burn, args.diagnostic_lags), device)
-            diag = dg.ChainDiagnostics(Q, C, d + 1, saved_iterations - burn, args.diagnostic_lags, device)
-            if burn == 0:
-                diag.accumulate(s.row0.unsqueeze(0).contiguous())
-        bmeans = None
-        if getattr(args, "diagnostic_batch_means", False):             # ESS / MCSE by batch means, fed exactly where the diagnostics are
-            from . import batch_means as bm
-            bm.check_memory(bm.workspace_bytes(Q, d + 1, C, saved_iterations - burn), device)
-            bmeans = bm.BatchMeans(Q, C, d + 1, saved_iterations - burn, device)
-            if burn == 0:
-                bmeans.accumulate(s.row0.unsqueeze(0).contiguous())
-        waic = None
-        if getattr(args, "waic", False):                               # WAIC over all chains, accumulated like the diagnostics
-            from . import waic as wc
-            from .PyHillFit import experiments_and_labels
-            wpts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
-            wc.check_memory(wc.workspace_bytes(Q, wpts.stride, C, saved_iterations - burn), device)
-            waic = wc.PointwiseWAIC(wpts, "hierarchical", Q, C, saved_iterations - burn, device)
-            if burn == 0:
-                waic.accumulate(s.row0.unsqueeze(0).contiguous())
-        psis = None
-        if getattr(args, "loo", False):                                # PSIS-LOO over all chains, accumulated like WAIC
-            from . import loo as lo
-            from . import waic as wc
-            from .PyHillFit import experiments_and_labels
-            lpts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
-            lo.check_memory(lo.workspace_bytes(Q, lpts.stride, C, saved_iterations - burn, args.loo_tail_per_chain), device)
-            psis = lo.PointwiseLOO(lpts, "hierarchical", Q, C, saved_iterations - burn, device, args.loo_tail_per_chain)
-            if burn == 0:
-                psis.accumulate(s.row0.unsqueeze(0).contiguous())
-        logo = None
-        if getattr(args, "leave_experiment_out", False):               # integrated leave-one-experiment-out, accumulated like PSIS-LOO
-            from . import marginal as mg
-            from . import waic as wc
-            from .PyHillFit import experiments_and_labels
-            mpts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
-            mg.check_memory(mg.workspace_bytes(Q, ne, C, saved_iterations - burn, args.marginal_every, seg // thinning), device)
-            logo = mg.ExperimentLOO(mpts, Q, C, saved_iterations - burn, args.marginal_nodes, args.marginal_every, device)
-            if burn == 0:
-                logo.accumulate(s.row0.unsqueeze(0).contiguous())
-        quant = None
-        if getattr(args, "quantiles", False):                          # posterior quantiles over all chains, accumulated like the diagnostics
-            from . import quantiles as qn
-            G = getattr(args, "predictive_bands", 0)
-            named = tuple(getattr(args, "band_concs", None) or ())
-            # the doses of the bands: G over the concentrations of the pair's fitted experiments, then the named ones
-            doses = [qn.band_doses(np.concatenate([np.asarray(e)[:, 0] for e in m[2]]), G, named) for m in members] if G else None
-            qn.check_memory(qn.workspace_bytes(Q, d + 1, 2 * (G + len(named)) if G else 0, args.quantile_bins), device)
-            quant = qn.PosteriorQuantiles(Q, C, d + 1, saved_iterations - burn, args.quantile_probs, args.quantile_bins, device,
-                                          band_ln_doses=np.log(np.array(doses)) if G else None, seed=args.seed,
-                                          problem_ids=[m[3] for m in members], chain_id_base=0)
-            quant.doses = doses
-            if burn == 0:
-                quant.accumulate(s.row0.unsqueeze(0).contiguous())
-        ppc = None
-        if getattr(args, "ppc", False):                                # posterior predictive checks, accumulated like WAIC
-            from . import ppc as pp
-            from . import waic as wc
-            from .PyHillFit import experiments_and_labels
-            ppts = wc.Points.hierarchical([m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])
-            pp.check_memory(pp.workspace_bytes(Q, ppts.stride, C, saved_iterations - burn), device)
-            ppc = pp.PosteriorPredictiveCheck(ppts, "hierarchical", Q, C, saved_iterations - burn, args.seed, [m[3] for m in members], 0,
-                                              device)
-            if burn == 0:
-                ppc.accumulate(s.row0.unsqueeze(0).contiguous())
-        sens = None
-        if getattr(args, "sensitivity", False):                        # power-scaling sensitivity, accumulated like the quantiles
-            from . import sensitivity as sn
-            sn.check_memory(sn.workspace_bytes(Q, d, C, saved_iterations - burn, args.sensitivity_bins), device)
-            sens = sn.PowerScaling(s.points, "hierarchical", Q, C, d, saved_iterations - burn, args.sensitivity_delta,
-                                   args.sensitivity_bins, device, prior=prior, threshold=args.sensitivity_threshold)
-            if burn == 0:
-                sens.accumulate(s.row0.unsqueeze(0).contiguous())
-        runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, curves=curves, files=files,
-                         diag=diag, bmeans=bmeans, waic=waic, psis=psis, logo=logo, quant=quant, ppc=ppc, sens=sens,
+        # the run analyses of the group, fed with its rows on its stream (analyses.py)
+        aset = an.AnalysisSet(kinds, an.Run(
+            args=args, kind="hierarchical", Q=Q, C=C, cols=d + 1, columns=hierarchical_columns(ne), saved=saved_iterations, burn=burn,
+            device=device, sampler_points=s.points, concs=[np.concatenate([np.asarray(e)[:, 0] for e in m[2]]) for m in members],
+            seed=args.seed, problem_ids=[m[3] for m in members], prior=prior, de=s.de, seg_rows=seg // thinning,
+            cdf_chains=cdf_chains(args, C), writers=writers, rng_pred=rng_pred, fitted_all=[m[4] for m in members],
+            make_points=lambda members=members, ne=ne: Points.hierarchical(
+                [m[2] for m in members], [experiments_and_labels(m[0], m[1], ne)[1] for m in members])))
+        aset.feed_start(s.row0)
+        runs.append(dict(ne=ne, members=members, theta0=theta0, s=s, kept=kept, buf=buf, seg=seg, r=1, files=files, analyses=aset,
                          stream=torch.cuda.Stream(device=device)))
     hint_side_by_side(r["s"] for r in runs)
     fused_runs = [r for r in runs if use_fused and (r["s"].n_expts, r["s"].points.packed.points_per_expt) in ISA_SHAPES]
@@ -706,25 +637,7 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
             nr = fused_rows[id(run)][1] if id(run) in fused_rows else s.rows_between(s.t, s.t + k)
             with torch.cuda.stream(run["stream"]):
                 rows = fused_rows[id(run)][0] if id(run) in fused_rows else s.advance(k, out=run["buf"][:nr])
-                first = max(0, burn - run["r"])                        # saved rows before `burn` are the burn-in (:84-86 of the CDF script)
-                if run["curves"] is not None and first < nr:
-                    run["curves"].accumulate(rows[first:], cdf_chains(args, args.num_chains))
-                if run["diag"] is not None and first < nr:
-                    run["diag"].accumulate(rows[first:])
-                if run["bmeans"] is not None and first < nr:
-                    run["bmeans"].accumulate(rows[first:])
-                if run["waic"] is not None and first < nr:
-                    run["waic"].accumulate(rows[first:])
-                if run["psis"] is not None and first < nr:
-                    run["psis"].accumulate(rows[first:])
-                if run["logo"] is not None and first < nr:
-                    run["logo"].accumulate(rows[first:])
-                if run["quant"] is not None and first < nr:
-                    run["quant"].accumulate(rows[first:])
-                if run["ppc"] is not None and first < nr:
-                    run["ppc"].accumulate(rows[first:])
-                if run["sens"] is not None and first < nr:
-                    run["sens"].accumulate(rows[first:])
+                run["analyses"].feed(rows, run["r"], nr)               # saved rows before `burn` are the burn-in (:84-86 of the CDF script)
                 run["kept"][run["r"]:run["r"] + nr].copy_(rows[:, :, :, 0], non_blocking=True)   # chain 0 of each pair
                 ev = torch.cuda.Event()
                 ev.record(run["stream"])
@@ -741,149 +654,33 @@ def run_hierarchical(pairs, args, device, rank=0, world=1):
         fused.check_queue()
     elapsed = time.time() - start
     total_chains = sum(len(r_["members"]) for r_ in runs) * args.num_chains
-    diag_names, diag_parts = [], []
-    waic_names, waic_parts = [], []
-    loo_names, loo_parts = [], []
-    quant_names, quant_parts = [], []
-    ppc_names, ppc_parts = [], []
-    sens_names, sens_parts = [], []
-    logo_names, logo_parts, logo_labels = [], [], []
-    de_names, de_parts = [], []
-    bm_parts = []
-    band_nf = 0
+    names = []
     for run in runs:
         ne, members, theta0, s, kept = run["ne"], run["members"], run["theta0"], run["s"], run["kept"]
         Q, C = len(members), args.num_chains
         mean, var, _ = s.posterior_moments()
         mean, var = mean.cpu().numpy(), var.cpu().numpy()
         acc = s.acceptance().cpu().numpy()
-        diag_res = run["diag"].result() if run["diag"] is not None else None
-        if diag_res is not None:
-            run["diag"].free()
-        bm_res = run["bmeans"].result() if run["bmeans"] is not None else None
-        if bm_res is not None:
-            run["bmeans"].free()
-        waic_res = run["waic"].result() if run["waic"] is not None else None
-        loo_res = run["psis"].result() if run["psis"] is not None else None
-        if loo_res is not None:
-            run["psis"].free()
-        logo_res = run["logo"].result() if run["logo"] is not None else None
-        if logo_res is not None:
-            run["logo"].free()
-        quant_res = run["quant"].result() if run["quant"] is not None else None
-        if quant_res is not None:
-            run["quant"].free()
-        ppc_res = run["ppc"].result() if run["ppc"] is not None else None
-        if ppc_res is not None:
-            run["ppc"].free()
-        sens_res = run["sens"].result() if run["sens"] is not None else None
-        if sens_res is not None:
-            run["sens"].free()
-        de_res = s.de.records() if s.de is not None else None
+        run["analyses"].finish()
         for q, (drug, channel, experiments, _, fitted_all) in enumerate(members):
             d_clean, c_clean, output_dir, chain_dir, figs_dir, chain_file = run["files"][q]
             chain0 = kept[:, q].numpy()
             writers.submit(chainio.save_alpha_mu_samples, dr.alpha_mu_downsampling(d_clean, c_clean),
                            chainio.pick_alpha_mu_rows(chain0, args.num_APs, burn, rng), d_clean, c_clean)   # :519-525
-            if run["curves"] is not None:
-                from .predictive import save_cdfs_and_samples
-                save_cdfs_and_samples(writers, d_clean, c_clean, ne, run["curves"].result(q), args.num_APs, rng_pred, fitted_all)
             summ = {"drug": d_clean, "channel": c_clean, "num_expts": ne, "chains": C, "iterations": total_iterations,
                     "pooled_mean": mean[:, q].mean(axis=1).tolist(),
                     "pooled_sd": np.sqrt(var[:, q].mean(axis=1) + mean[:, q].var(axis=1)).tolist(),
                     "acceptance": float(acc[q].mean()), "first_iteration": theta0[q].tolist(),
                     "mh_samples_per_second": total_chains * total_iterations / elapsed}
-            if diag_res is not None:
-                summ["diagnostics"] = dg.json_record(diag_res, q, args.diagnostic_lags, saved_iterations - burn, C,
-                                                     columns=hierarchical_columns(ne))
-                diag_names.append("{} + {}".format(d_clean, c_clean))
-                diag_parts.append((diag_res["rhat"][q], diag_res["ess"][q]))
-                if de_res is not None:
-                    from . import de_moves as de
-                    summ["diagnostics"]["chains_coupled_within_populations_of"] = s.de.G
-                    summ["diagnostics"]["note"] = de.COUPLING_NOTE.format(G=s.de.G)
-                if bm_res is not None:
-                    from . import batch_means as bm
-                    summ["diagnostics"]["batch_means"] = bm.json_record(bm_res, q, de_coupled=de_res is not None)
-                    bm_parts.append((bm_res["ess"][q], bm_res["tau"][q]))
-            if de_res is not None:
-                summ["de_moves"] = de_res[q]
-                de_names.append("{} + {}".format(d_clean, c_clean))
-                de_parts.append(de_res[q])
-            if waic_res is not None:
-                from . import waic as wc
-                summ["waic"] = wc.json_record(waic_res[q], run["waic"].points, q)
-                waic_names.append("{} + {}".format(d_clean, c_clean))
-                waic_parts.append(waic_res[q])
-            if loo_res is not None:
-                from . import loo as lo
-                summ["loo"] = lo.json_record(loo_res[q], run["psis"].points, q, run["psis"].M, run["psis"].k)
-                loo_names.append("{} + {}".format(d_clean, c_clean))
-                loo_parts.append(loo_res[q])
-            if logo_res is not None:
-                from . import marginal as mg
-                labels = [e[0] for e in run["logo"].epoints.info[q]]
-                summ["loo_experiment"] = mg.json_record(logo_res[q], labels, run["logo"].nodes, run["logo"].every)
-                logo_names.append("{} + {}".format(d_clean, c_clean))
-                logo_parts.append(logo_res[q])
-                logo_labels.append(labels)
-            if quant_res is not None:
-                from . import quantiles as qn
-                summ["quantiles"] = qn.json_record(quant_res, q, hierarchical_columns(ne), args.quantile_bins)
-                quant_names.append("{} + {}".format(d_clean, c_clean))
-                nc = int(quant_res["columns"])                          # the band slots follow the columns
-                quant_parts.append((quant_res["bin_width"][q, :nc], quant_res["min"][q, :nc], quant_res["max"][q, :nc],
-                                    quant_res["non_finite"][q, :nc]))
-                if run["quant"].doses is not None:
-                    summ["hierarchical_bands"] = qn.hier_band_record(quant_res, q, run["quant"].doses[q], args.predictive_bands)
-                    band_nf += int(np.sum(quant_res["non_finite"][q, nc:]))
-            if ppc_res is not None:
-                from . import ppc as pp
-                summ["ppc"] = pp.json_record(ppc_res[q], run["ppc"].points, q)
-                ppc_names.append("{} + {}".format(d_clean, c_clean))
-                ppc_parts.append(ppc_res[q])
-            if sens_res is not None:
-                from . import sensitivity as sn
-                summ["sensitivity"] = sn.json_record(sens_res, q, hierarchical_columns(ne)[:5 + 2 * ne])
-                sens_names.append("{} + {}".format(d_clean, c_clean))
-                sens_parts.append(sn.part_of(sens_res, q))
+            run["analyses"].record(summ, q)
+            names.append("{} + {}".format(d_clean, c_clean))
             with open(chain_file[:-4] + "_summary.json", "w") as f:
                 json.dump(summ, f, indent=1)
             summaries.append(summ)
     writers.close()
     chain_streams.close()
-    if getattr(args, "diagnostics", False):
-        print(dg.report_line(rank, diag_names, [p_[0] for p_ in diag_parts], [p_[1] for p_ in diag_parts]))
-        if getattr(args, "de_every", 0):
-            from . import de_moves as de
-            print("diagnostics [rank {}]: {}".format(rank, de.COUPLING_NOTE.format(G=args.de_population)))
-        if getattr(args, "diagnostic_batch_means", False):
-            from . import batch_means as bm
-            print(bm.report_line(rank, diag_names, [p_[1] for p_ in diag_parts], [p_[0] for p_ in bm_parts], [p_[1] for p_ in bm_parts],
-                                 thinning))
-            if getattr(args, "de_every", 0):
-                print("batch means [rank {}]: {}".format(rank, bm.DE_NOTE))
-    if getattr(args, "de_every", 0):
-        from . import de_moves as de
-        print(de.report_line(rank, de_names, de_parts))
-    if getattr(args, "waic", False):
-        from . import waic as wc
-        print(wc.report_line(rank, waic_names, waic_parts))
-    if getattr(args, "loo", False):
-        from . import loo as lo
-        print(lo.report_line(rank, loo_names, loo_parts))
-    if getattr(args, "leave_experiment_out", False):
-        from . import marginal as mg
-        print(mg.report_line(rank, logo_names, logo_parts, logo_labels))
-    if getattr(args, "quantiles", False):
-        from . import quantiles as qn
-        print(qn.report_line(rank, quant_names, quant_parts, band_nf if getattr(args, "predictive_bands", 0) else None))
-    if getattr(args, "ppc", False):
-        from . import ppc as pp
-        print(pp.report_line(rank, ppc_names, ppc_parts))
-    if getattr(args, "sensitivity", False):
-        from . import sensitivity as sn
-        print(sn.report_line(rank, sens_names, sens_parts))
+    for line in an.report(kinds, [run["analyses"] for run in runs], rank, names, args):
+        print(line)
     print("timing [rank {}]: data + start points {:.1f} s, sampling {:.1f} s ({} chains x {} iterations), chain files {:.1f} s".format(
         rank, start - t_begin, elapsed, total_chains, total_iterations, time.time() - start - elapsed))
     return summaries

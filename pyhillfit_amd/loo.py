@@ -26,7 +26,8 @@ import torch
 
 from . import _lib
 from .sampler import _ptr, _stream_ptr
-from .waic import GIVEN, DevicePoints, _likelihood, _num, columns_read
+from ._lib import _num
+from .waic import GIVEN, DevicePoints, _likelihood, columns_read
 
 HIERARCHICAL = 3
 METHOD = ("PSIS-LOO (Vehtari, Simpson, Gelman, Yao & Gabry 2024; r_eff = 1): log ratios r = -log p(y_i | theta_s) over all chains' "
@@ -222,11 +223,3 @@ def report_line(rank, names, results):
     return ("loo [rank {}]: {} problems, {} with some k-hat > threshold ({:.2f}); worst k-hat {:.3f} ({}); {} undetermined points in "
             "{} problems".format(rank, len(names), flagged, results[0]["khat_threshold"], worst[w], names[w], sum(und),
                                  sum(1 for u in und if u)))
-
-
-def check_memory(nbytes, device):
-    """refuse to start when the workspace would take more than 80 % of the free device memory (as --waic does)"""
-    free = torch.cuda.mem_get_info(device)[0]
-    if nbytes > 0.8 * free:
-        raise SystemExit("--loo needs {:.1f} GB of device memory for its workspace, {:.1f} GB are free: select fewer pairs, fewer chains "
-                         "or a smaller --loo-tail-per-chain".format(nbytes / 1e9, free / 1e9))

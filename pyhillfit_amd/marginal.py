@@ -20,7 +20,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import diagnostics as dg
 from . import loo as loo_mod
 from . import waic as waic_mod
 from .sampler import _ptr, _stream_ptr
@@ -258,7 +257,7 @@ def finalize(elpd_i, lppd_i, khat_i, determined_i, lse_i, var_i, gap_max_i, n_i,
 
 def json_record(res, labels, nodes, every):
     """the summary's "loo_experiment" object of one problem (NaN and infinities -> null); labels: the experiments' labels in the data file"""
-    num = waic_mod._num
+    num = _lib._num
     rec = {k: (num(res[k]) if isinstance(res[k], float) else res[k]) for k in
            ("elpd_logo", "se_elpd_logo", "p_logo", "lppd", "elpd_waic", "n_experiments", "khat_threshold", "n_khat_above_threshold",
             "n_gap_above_0.01", "max_khat", "n_undetermined", "draws")}
@@ -289,7 +288,3 @@ def report_line(rank, names, results, labels=None):
         shown = ", ".join(wide[:8]) + (", ... (%d in all)" % len(wide) if len(wide) > 8 else "")
         line += "; quadrature gap above {} in {}: raise --marginal-nodes".format(GAP_WARN, shown)
     return line
-
-
-def check_memory(nbytes, device):
-    dg.check_memory(nbytes, device, what="--leave-experiment-out")

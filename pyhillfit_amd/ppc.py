@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import diagnostics as dg
+from ._lib import _num
 from . import waic as wc
 from .sampler import _ptr, _stream_ptr
 
@@ -165,11 +165,6 @@ def ppc_of_draws(points, kind, draws, seed=25, problem_id=0, chain_id_base=0, de
     return p.result()[0]
 
 
-def _num(v):
-    v = float(v)
-    return None if not np.isfinite(v) else v
-
-
 def json_record(res, points, q):
     """the summary's "ppc" object of problem q (NaN -> null); per-point arrays in data-file order"""
     info = points.info[q]
@@ -197,7 +192,3 @@ def report_line(rank, names, results):
         line += "; most extreme: {} ({} p = {:.4g})".format(*worst)
     return line + "; {} of {} points with PIT outside [{}, {}]".format(sum(r["n_flagged"] for r in results), sum(r["n_points"] for r in results),
                                                                   PIT_LO, PIT_HI)
-
-
-def check_memory(nbytes, device):
-    dg.check_memory(nbytes, device, what="--ppc")

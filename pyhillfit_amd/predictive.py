@@ -74,6 +74,10 @@ class PredictiveCurves(object):
         m = self.means()[q].cpu().numpy()
         return self.hill_x_host, m[0], self.pic50_x_host, m[1], m[2], m[3]
 
+    def free(self):
+        self.sums = None
+        self.scratch = None
+
 
 def curves_from_chains(chains, device, chunk=DEFAULT_CHUNK):
     """chains: list of arrays [rows_i][>=4] (alpha, beta, mu, s first; burn-in already dropped, equal row counts batch

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
 DEFAULT_PROBS = (0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975)
@@ -238,11 +239,6 @@ def exact_quantiles(draws, probs=DEFAULT_PROBS):
     return out
 
 
-def _num(v):
-    v = float(v)
-    return None if not np.isfinite(v) else v
-
-
 def _intervals(probs, value, lo, hi):
     rec = {}
     for name, (pl, ph) in INTERVALS.items():
@@ -344,11 +340,3 @@ def report_line(rank, names, parts, band_non_finite=None):
     if band_non_finite is not None:
         line += "; {} non-finite band draws".format(int(band_non_finite))
     return line
-
-
-def check_memory(nbytes, device, what="--quantiles"):
-    """refuse to start when the workspace would take more than 80 % of the free device memory"""
-    free = torch.cuda.mem_get_info(device)[0]
-    if nbytes > 0.8 * free:
-        raise SystemExit("{} needs {:.1f} GB of device memory for its histograms, {:.1f} GB are free: select fewer pairs, fewer "
-                         "curve points or a smaller --quantile-bins".format(what, nbytes / 1e9, free / 1e9))

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
 METHOD = ("replica exchange between adjacent rungs (deterministic even-odd scheme, Syed et al. 2022): after every K iterations round "
@@ -201,11 +202,6 @@ def unit_columns(stats, rounds, num_pairs, rungs, se_joint=None, ti_se=None):
         v[u, 4] = np.nan if se_joint is None else se_joint[p]
         v[u, 5] = np.nan if ti_se is None else ti_se[p]
     return v
-
-
-def _num(v):
-    v = float(v)
-    return v if np.isfinite(v) else None
 
 
 def json_record(unit_values, temperatures, chains, every):

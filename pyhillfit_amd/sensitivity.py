@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import _num
 
 DEFAULT_DELTA = 0.01
 DEFAULT_BINS = 4096
@@ -66,15 +67,6 @@ def workspace_bytes(num_problems, columns, chains, total_rows, bins=DEFAULT_BINS
     if n == 0:
         raise ValueError(lib.phf_last_error().decode())
     return int(n)
-
-
-def check_memory(nbytes, device, what="--sensitivity"):
-    """refuse to start when the workspace would take more than 80 % of the free device memory"""
-    import torch
-    free = torch.cuda.mem_get_info(device)[0]
-    if nbytes > 0.8 * free:
-        raise SystemExit("{} needs {:.1f} GB of device memory for its histograms, {:.1f} GB are free: select fewer pairs or a smaller "
-                         "--sensitivity-bins".format(what, nbytes / 1e9, free / 1e9))
 
 
 class PowerScaling(object):
@@ -265,11 +257,6 @@ def finalize(slots, weights, cols, delta, threshold=DEFAULT_THRESHOLD, draws=Non
            "diagnosis": np.array([[diagnose(D[q, c, 0], D[q, c, 1], threshold) for c in range(nc)] for q in range(Qn)], dtype=object)}
     res["non_finite"] = (float(draws) - wq[..., 0, 0]) if draws is not None else np.full((Qn, 2), np.nan)
     return res
-
-
-def _num(v):
-    v = float(v)
-    return None if not np.isfinite(v) else v
 
 
 def json_record(res, q, columns):

@@ -22,7 +22,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import diagnostics as dg
 from .sampler import DevicePoints, _ptr, _stream_ptr
 
 FIELDS = ("m", "s1", "s2", "sum_ll", "n")
@@ -45,10 +44,6 @@ def workspace_bytes(num_problems, chains, total_rows):
     if n == 0:
         raise ValueError(lib.phf_last_error().decode())
     return int(n)
-
-
-def check_memory(nbytes, device):
-    dg.check_memory(nbytes, device, what="--stepping-stone")
 
 
 def chain_accumulators(ll, delta):

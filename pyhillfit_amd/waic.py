@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import diagnostics as dg
+from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
 P_WARN = 0.4
@@ -238,11 +238,6 @@ def waic_of_draws(points, kind, draws, device="cuda"):
     return w.result()[0]
 
 
-def _num(v):
-    v = float(v)
-    return None if not np.isfinite(v) else v
-
-
 def json_record(res, points, q):
     """the summary's "waic" object of problem q (NaN -> null); pointwise arrays in data-file order"""
     rec = {k: (_num(res[k]) if isinstance(res[k], float) else res[k]) for k in
@@ -262,7 +257,3 @@ def report_line(rank, names, results):
     w = int(np.argmax(warn))
     return ("waic [rank {}]: {} problems, {} with some p_waic_i > {}; sum of elpd_waic {:.2f}; most such points: {} ({})"
             .format(rank, len(names), sum(1 for v in warn if v > 0), P_WARN, sum(r["elpd_waic"] for r in results), names[w], warn[w]))
-
-
-def check_memory(nbytes, device):
-    dg.check_memory(nbytes, device, what="--waic")
