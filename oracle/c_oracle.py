@@ -243,6 +243,26 @@ def hier_state_covariance(st, dim):
     return (tri * dvec[None, :]) @ tri.T
 
 
+def grid_w0(anchor):
+    """the histogram grid's base width for an anchor (phf_grid.h: phf_grid_w0)"""
+    L = lib()
+    L.phfo_grid_w0.restype = C.c_double
+    return float(L.phfo_grid_w0(C.c_double(anchor)))
+
+
+def grid_bins(anchor, k, B, x):
+    """(t, binned, bin) of the values x on the grid of `anchor` at level k of B bins; bin is -1 where the value is not binned"""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    t, binned, j = np.empty(x.size), np.empty(x.size, dtype=np.int32), np.empty(x.size, dtype=np.int32)
+    lib().phfo_grid_bins(C.c_double(anchor), C.c_int(k), C.c_int(B), C.c_int64(x.size), _p(x), _p(t), _p(binned), _p(j))
+    return t, binned.astype(bool), j
+
+
+def grid_holds(tmin, tmax, k, B):
+    """do the B bins of level k hold [tmin, tmax] (phf_grid.h: phf_grid_holds)"""
+    return bool(lib().phfo_grid_holds(C.c_double(tmin), C.c_double(tmax), C.c_int(k), C.c_int(B)))
+
+
 def predictive_accumulate(rows, chains_used, hill_x, pic50_x, chunk, sums=None):
     """twin of phf_predictive_accumulate: rows [num_rows][Q][row_stride][C] -> sums [Q][4][G] (added to `sums`)."""
     rows = np.ascontiguousarray(rows, dtype=np.float64)

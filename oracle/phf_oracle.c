@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "../pyhillfit_amd/csrc/phf_model.h"
+#include "../pyhillfit_amd/csrc/phf_grid.h"
 #include "../pyhillfit_amd/csrc/phf_hier_model.h"
 #include "../pyhillfit_amd/csrc/phf_predictive_model.h"
 
@@ -319,6 +320,21 @@ void phfo_draws(int d, uint32_t chain_id, uint32_t problem_id, uint32_t t, uint3
                 double* z /* [4] */, double* log_u) {
   *log_u = phf_mh_draws(d, chain_id, problem_id, t, seed_lo, seed_hi, phf_k_log, z);
 }
+
+/* ---- the histogram grid's scalar rule (phf_grid.h), as the kernels compile it ---- */
+double phfo_grid_w0(double anchor) { return phf_grid_w0(anchor); }
+
+/* per value: the grid coordinate t, whether the value is binned, and its bin at level k of B bins (-1 where it is not binned) */
+void phfo_grid_bins(double anchor, int k, int B, int64_t n, const double* x, double* t, int32_t* binned, int32_t* bin) {
+  const double inv_w0 = 1.0 / phf_grid_w0(anchor);
+  for (int64_t i = 0; i < n; ++i) {
+    t[i] = phf_grid_t(x[i], anchor, inv_w0);
+    binned[i] = phf_grid_binned(x[i], anchor, inv_w0);
+    bin[i] = binned[i] ? phf_grid_bin(t[i], k, B) : -1;
+  }
+}
+
+int phfo_grid_holds(double tmin, double tmax, int k, int B) { return phf_grid_holds(tmin, tmax, k, B); }
 
 /* ---- posterior-predictive curves: twin of phf_predictive_accumulate (python/construct_hierarchical_cdfs.py:32-58) ----
  * rows host [num_rows][num_problems][row_stride][num_chains]; sums host [num_problems][4][grid_points], added to.

@@ -16,6 +16,7 @@
 #include "../../include/pyhillfit_amd.h"
 #include "phf_batch_means.h"
 #include "phf_common.h"
+#include "phf_device_util.h"
 
 namespace {
 
@@ -45,12 +46,6 @@ __global__ __launch_bounds__(kThreads) void batch_means_accumulate_kernel(const 
   const double* xr = a.rows + ((size_t)q * a.stride + j) * a.C + c;
   double* st = a.ws + (size_t)qj * PHF_BM_FIELDS(a.nl) * a.C + c;
   phf_bm_rows(xr, rstep, a.nr, a.m0, a.half, st, (size_t)a.C, a.nl);
-}
-
-__device__ inline double wave_sum(double v) {
-  _Pragma("unroll")
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // out[q][j][l] = mean over the 2C half-chains of the variance of the batch means of level l, l = 0..nl-2 (l = 0: W);
@@ -95,8 +90,6 @@ __global__ __launch_bounds__(kThreads) void batch_means_reduce_kernel(const BmAr
     if (lane == 0) { o[nl - 1] = mean; o[nl] = v / (M - 1.0); }
   }
 }
-
-unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // shared argument checks of the four entries; on success *nl = floor(log2 h) + 1
 int check_shape(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows, int* nl) {

@@ -26,6 +26,7 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
+#include "phf_device_util.h"
 
 #define PHF_DIAG_UNROLL _Pragma("unroll")
 
@@ -174,12 +175,6 @@ __global__ __launch_bounds__(kThreads) void diag_close_kernel(const DiagArgs a) 
   st[(size_t)a.lay.xbar(a.half) * C] = st[a.lay.x0() * C] + ybar;
 }
 
-__device__ inline double wave_sum(double v) {
-  PHF_DIAG_UNROLL
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // out[q][j][k] = mean over the 2C half-chains of acov(k), k = 0..L; out[q][j][L+1] = mean of the half-chain means;
 // out[q][j][L+2] = their variance (divisor 2C - 1) = B/h.  One wavefront per (problem, column, k in 0..L+1).
 __global__ __launch_bounds__(kThreads) void diag_reduce_kernel(const DiagArgs a) {
@@ -211,8 +206,6 @@ __global__ __launch_bounds__(kThreads) void diag_reduce_kernel(const DiagArgs a)
     if (lane == 0) { o[L + 1] = mean; o[L + 2] = v / (M - 1.0); }
   }
 }
-
-unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // shared argument checks of the four entries; on success fills the layout
 int check_shape(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags, Layout* lay) {

@@ -20,19 +20,14 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
-#include "phf_pointwise.h"
+#include "phf_point_block.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kPtBlock = 4;             // points per wavefront of the accumulate kernel
+static_assert(kWaves == kPtWaves, "the accumulate kernel is launched with the point-block mapping's workgroup");
 constexpr int kFields = 5;              // m, s, x0, A, B
-constexpr int kHierarchical = 3;        // `likelihood` of the hierarchical layout (1 | 2: single-level model 1 | 2)
-constexpr int kGiven = 4;               // phf_waic_accumulate_given: l of point p is column p of the row
-
-__device__ inline int clamp_tag(int t, int hi) { return t < 0 ? 0 : (t > hi ? hi : t); }
-__device__ inline int clamp_count(int n, int stride) { return n < 0 ? 0 : (n > stride ? stride : n); }
 
 // ---- batch evaluators ------------------------------------------------------------------------------------------------------------
 template <int MODEL>
@@ -114,69 +109,26 @@ template <int LIK>
 __global__ __launch_bounds__(kThreads) void waic_accumulate_kernel(const WaicArgs a) {
   PHF_MATH_TABLES_TO_LDS();
   if (LIK == kGiven) { } else if (LIK == kHierarchical) PHF_ERFC_TABLE_TO_LDS(); else PHF_LOGPHI_TABLE_TO_LDS();
-  const int unit = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / 64));   // wave-uniform
-  if (unit >= a.units) return;
-  const int pb = unit % a.npb;
-  const int cg = (unit / a.npb) % a.ncg;
-  const int q = unit / a.npb / a.ncg;
-  const int ps = a.pts.stride;
-  const int n = clamp_count(a.pts.count[q], ps);
-  const int p0 = pb * kPtBlock;
-  if (p0 >= n) return;
-  const int np = n - p0 < kPtBlock ? n - p0 : kPtBlock;
-  const int c = cg * 64 + (threadIdx.x & 63);
-  if (c >= a.C) return;
+  phf_point_block b;
+  if (!phf_point_block_open<LIK>(a, b)) return;
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
   PHF_KFETCH_V(k_log, phf_k_log, PHF_K_LOG_N);
   const size_t C = (size_t)a.C;
-  double lc[kPtBlock], yv[kPtBlock], acc[kPtBlock][kFields];
-  int tg[kPtBlock];
-  double* st = a.ws + ((size_t)q * ps + p0) * kFields * C + c;
+  double acc[kPtBlock][kFields];
+  double* st = a.ws + ((size_t)b.q * a.pts.stride + b.p0) * kFields * C + b.c;
 #pragma unroll
-  for (int k = 0; k < kPtBlock; ++k) {
-    const int p = k < np ? p0 + k : p0;                            // a block's missing points repeat its first (never stored)
-    const size_t at = (size_t)q * ps + p;
-    lc[k] = LIK == kGiven ? 0.0 : a.pts.ln_conc[at];
-    yv[k] = LIK == kGiven ? 0.0 : a.pts.response[at];
-    tg[k] = LIK == kGiven ? 0 : clamp_tag(a.pts.tag[at], LIK == kHierarchical ? a.ne - 1 : 2);
+  for (int k = 0; k < kPtBlock; ++k)
 #pragma unroll
-    for (int f = 0; f < kFields; ++f) acc[k][f] = k < np ? st[((size_t)k * kFields + f) * C] : 0.0;
-  }
-  const size_t rstep = (size_t)a.Q * a.stride_cols * C;
-  const double* xr = a.rows + (size_t)q * a.stride_cols * C + c;
+    for (int f = 0; f < kFields; ++f) acc[k][f] = k < b.np ? st[((size_t)k * kFields + f) * C] : 0.0;
   for (int64_t r = 0; r < a.nr; ++r) {
-    const double* x = xr + (size_t)r * rstep;
     const bool first = a.first_row + r == 0;
-    if (LIK == kGiven) {
-#pragma unroll
-      for (int k = 0; k < kPtBlock; ++k)
-        if (k < np) waic_update(x[(size_t)(p0 + k) * C], first, acc[k][0], acc[k][1], acc[k][2], acc[k][3], acc[k][4], k_exp);
-    } else if (LIK == kHierarchical) {
-      const phf_pw_sigma sg = phf_pw_sigma_terms(x[(size_t)(4 + 2 * a.ne) * C], k_log);
-#pragma unroll
-      for (int k = 0; k < kPtBlock; ++k) {
-        if (k < np) {
-          const double ln_ic50 = PHF_LN10 * (6.0 - x[(size_t)(4 + 2 * tg[k]) * C]);
-          const double l = phf_pw_hier_point(lc[k], yv[k], x[(size_t)(5 + 2 * tg[k]) * C], ln_ic50, sg, k_exp, k_log);
-          waic_update(l, first, acc[k][0], acc[k][1], acc[k][2], acc[k][3], acc[k][4], k_exp);
-        }
-      }
-    } else {
-      const double pic50 = x[0], hill = LIK == 2 ? x[C] : 1.0;
-      const double ln_ic50 = PHF_LN10 * (6.0 - pic50);
-      const phf_pw_sigma sg = phf_pw_sigma_terms(x[(size_t)LIK * C], k_log);
-#pragma unroll
-      for (int k = 0; k < kPtBlock; ++k) {
-        if (k < np) {
-          const double l = phf_pw_sl_point(LIK, lc[k], yv[k], tg[k], hill, ln_ic50, sg, k_exp);
-          waic_update(l, first, acc[k][0], acc[k][1], acc[k][2], acc[k][3], acc[k][4], k_exp);
-        }
-      }
-    }
+    phf_point_block_row<LIK>(a, b, b.xr + (size_t)r * b.rstep, k_exp, k_log, [&](int k, double l) {
+      waic_update(l, first, acc[k][0], acc[k][1], acc[k][2], acc[k][3], acc[k][4], k_exp);
+    });
   }
 #pragma unroll
   for (int k = 0; k < kPtBlock; ++k)
-    if (k < np) {
+    if (k < b.np) {
 #pragma unroll
       for (int f = 0; f < kFields; ++f) st[((size_t)k * kFields + f) * C] = acc[k][f];
     }
@@ -233,8 +185,6 @@ __global__ __launch_bounds__(kThreads) void waic_reduce_kernel(const WaicArgs a)
     a.out[plane + at] = acc.m2 / (acc.n - 1.0);
   }
 }
-
-unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 int check_shape(const char* who, int num_problems, int stride, int num_chains, int64_t total_rows) {
   char msg[kPhfErrorBufferSize];

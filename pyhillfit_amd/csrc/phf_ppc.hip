@@ -21,21 +21,18 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
+#include "phf_point_block.h"
 #include "phf_ppc.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kPtBlock = 4;             // points per wavefront of the PIT kernel
+static_assert(kWaves == kPtWaves, "the PIT kernel is launched with the point-block mapping's workgroup");
 constexpr int kStats = PHF_PPC_STATS;
 constexpr int kInvalid = 4 * kStats;    // field of the invalid-draw count
 constexpr int kHead = kInvalid + 1;     // first PIT field
 constexpr int kMaxStride = 512;         // points per problem: the statistics kernel's LDS (4 x 512 x 20 bytes)
-constexpr int kHierarchical = 3;
-
-__device__ inline int clamp_tag(int t, int hi) { return t < 0 ? 0 : (t > hi ? hi : t); }
-__device__ inline int clamp_count(int n, int stride) { return n < 0 ? 0 : (n > stride ? stride : n); }
 
 template <int LIK>
 __device__ inline double sigma_of(const double* x, size_t cs, int ne) {
@@ -204,59 +201,39 @@ template <int LIK>
 __global__ __launch_bounds__(kThreads) void ppc_pit_kernel(const PpcArgs a) {
   PHF_MATH_TABLES_TO_LDS();
   if (LIK == kHierarchical) PHF_ERFC_TABLE_TO_LDS();
-  const int unit = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / 64));   // wave-uniform
-  if (unit >= a.units) return;
-  const int pb = unit % a.npb;
-  const int cg = (unit / a.npb) % a.ncg;
-  const int q = unit / a.npb / a.ncg;
-  const int ps = a.pts.stride;
-  const int n = clamp_count(a.pts.count[q], ps);
-  const int p0 = pb * kPtBlock;
-  if (p0 >= n) return;
-  const int np = n - p0 < kPtBlock ? n - p0 : kPtBlock;
-  const int c = cg * 64 + (threadIdx.x & 63);
-  if (c >= a.C) return;
+  phf_point_block b;
+  if (!phf_point_block_open<LIK>(a, b)) return;
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
   const size_t C = (size_t)a.C;
-  double lc[kPtBlock], yv[kPtBlock], acc[kPtBlock];
-  int tg[kPtBlock];
-  double* st = a.ws + ((size_t)q * fields_of(ps) + kHead + p0) * C + c;
+  double acc[kPtBlock];
+  double* st = a.ws + ((size_t)b.q * fields_of(a.pts.stride) + kHead + b.p0) * C + b.c;
 #pragma unroll
-  for (int k = 0; k < kPtBlock; ++k) {
-    const int p = k < np ? p0 + k : p0;                            // a block's missing points repeat its first (never stored)
-    const size_t at = (size_t)q * ps + p;
-    lc[k] = a.pts.ln_conc[at];
-    yv[k] = a.pts.response[at];
-    tg[k] = clamp_tag(a.pts.tag[at], LIK == kHierarchical ? a.ne - 1 : 2);
-    acc[k] = k < np ? st[(size_t)k * C] : 0.0;
-  }
-  const size_t rstep = (size_t)a.Q * a.stride_cols * C;
-  const double* xr = a.rows + (size_t)q * a.stride_cols * C + c;
+  for (int k = 0; k < kPtBlock; ++k) acc[k] = k < b.np ? st[(size_t)k * C] : 0.0;
   for (int64_t r = 0; r < a.nr; ++r) {
-    const double* x = xr + (size_t)r * rstep;
+    const double* x = b.xr + (size_t)r * b.rstep;
     const double sigma = sigma_of<LIK>(x, C, a.ne);
     if (!valid_sigma(sigma)) continue;
     const double inv_s = phf_rcp(sigma);
     if (LIK == kHierarchical) {
 #pragma unroll
       for (int k = 0; k < kPtBlock; ++k) {
-        if (k < np) {
-          const double li = PHF_LN10 * (6.0 - x[(size_t)(4 + 2 * tg[k]) * C]);
-          const double pred = phf_pw_pred(2, lc[k], x[(size_t)(5 + 2 * tg[k]) * C], li, k_exp);
-          acc[k] += phf_ppc_pit_hier(pred, yv[k], inv_s, k_exp);
+        if (k < b.np) {
+          const double li = PHF_LN10 * (6.0 - x[(size_t)(4 + 2 * b.tg[k]) * C]);
+          const double pred = phf_pw_pred(2, b.lc[k], x[(size_t)(5 + 2 * b.tg[k]) * C], li, k_exp);
+          acc[k] += phf_ppc_pit_hier(pred, b.yv[k], inv_s, k_exp);
         }
       }
     } else {
       const double ln_ic50 = PHF_LN10 * (6.0 - x[0]), hill = LIK == 2 ? x[C] : 1.0;
 #pragma unroll
       for (int k = 0; k < kPtBlock; ++k) {
-        if (k < np) acc[k] += phf_ppc_pit_sl(phf_pw_pred(LIK, lc[k], hill, ln_ic50, k_exp), yv[k], tg[k], inv_s);
+        if (k < b.np) acc[k] += phf_ppc_pit_sl(phf_pw_pred(LIK, b.lc[k], hill, ln_ic50, k_exp), b.yv[k], b.tg[k], inv_s);
       }
     }
   }
 #pragma unroll
   for (int k = 0; k < kPtBlock; ++k)
-    if (k < np) st[(size_t)k * C] = acc[k];
+    if (k < b.np) st[(size_t)k * C] = acc[k];
 }
 
 // out[u] = the sum over chains of workspace field u (u = q * fields + f), chains in a fixed order
@@ -304,8 +281,6 @@ __global__ __launch_bounds__(kThreads) void ppc_replicate_kernel(const phf_point
                       counter[3 * i + 2], k0, k1, oc, k_exp, k_log, yo, so, so + kStats);
   for (int p = n; p < pts.stride; ++p) yo[p] = PHF_NAN;
 }
-
-unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 int check_shape(const char* who, int num_problems, int stride, int num_chains, int64_t total_rows) {
   char msg[kPhfErrorBufferSize];

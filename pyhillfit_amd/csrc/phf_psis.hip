@@ -43,17 +43,15 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
-#include "phf_pointwise.h"
+#include "phf_point_block.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kPtBlock = 4;             // points per wavefront of the accumulate kernel
+static_assert(kWaves == kPtWaves, "the accumulate kernel is launched with the point-block mapping's workgroup");
 constexpr int kFields = 6;              // m_nt, s_nt, m_all, s_all, fill, inserts
 constexpr int kOut = 5;                 // elpd_loo, lppd, k-hat, sigma-hat, determined
-constexpr int kHierarchical = 3;        // `likelihood` of the hierarchical layout (1 | 2: single-level model 1 | 2)
-constexpr int kGiven = 4;               // phf_psis_accumulate_given: l of point p is column p of the row
 constexpr int kLdsTail = 8192;          // tail entries (M + 1) the reduce keeps in LDS; beyond, the HBM scratch
 constexpr int64_t kMaxTail = (1 << 20) - 1;   // the longest tail M accepted
 constexpr int kMaxGrid = 30 + 1024;     // Zhang-Stephens grid points: 30 + floor(sqrt(M)) <= 30 + 1023
@@ -62,9 +60,6 @@ constexpr double kEps = 2.220446049250313e-16;
 constexpr int64_t kThresholdRows = 1024;                  // T is recomputed after every 1024th row up to row 8192, then every 8192nd
 constexpr int64_t kThresholdRowsLate = 8192;
 constexpr double kExactBudget = 32.0 * 1024 * 1024 * 1024;  // default: k = M + 1 while the workspace stays within 32 GiB
-
-__device__ inline int clamp_tag(int t, int hi) { return t < 0 ? 0 : (t > hi ? hi : t); }
-__device__ inline int clamp_count(int n, int stride) { return n < 0 ? 0 : (n > stride ? stride : n); }
 
 int64_t tail_length_of(int64_t S) {
   const double s = (double)S;
@@ -162,37 +157,23 @@ template <int LIK>
 __global__ __launch_bounds__(kThreads) void psis_accumulate_kernel(const PsisArgs a) {
   PHF_MATH_TABLES_TO_LDS();
   if (LIK == kGiven) { } else if (LIK == kHierarchical) PHF_ERFC_TABLE_TO_LDS(); else PHF_LOGPHI_TABLE_TO_LDS();
-  const int unit = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / 64));   // wave-uniform
-  if (unit >= a.units) return;
-  const int pb = unit % a.npb;
-  const int cg = (unit / a.npb) % a.ncg;
-  const int q = unit / a.npb / a.ncg;
-  const int ps = a.pts.stride;
-  const int n = clamp_count(a.pts.count[q], ps);
-  const int p0 = pb * kPtBlock;
-  if (p0 >= n) return;
-  const int np = n - p0 < kPtBlock ? n - p0 : kPtBlock;
-  const int c = cg * 64 + (threadIdx.x & 63);
-  if (c >= a.C) return;
+  phf_point_block b;
+  if (!phf_point_block_open<LIK>(a, b)) return;
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
   PHF_KFETCH_V(k_log, phf_k_log, PHF_K_LOG_N);
   const size_t C = (size_t)a.C;
   const int K = a.k;
   const bool fresh = a.first_row == 0;
-  double lc[kPtBlock], yv[kPtBlock], h[kPtBlock], thr[kPtBlock], m_nt[kPtBlock], s_nt[kPtBlock], m_all[kPtBlock], s_all[kPtBlock], ins[kPtBlock];
-  int tg[kPtBlock], f[kPtBlock];
-  double* st = a.fields + ((size_t)q * ps + p0) * kFields * C + c;
-  double* hp = a.heap + ((size_t)q * ps + p0) * K * C + c;
+  double h[kPtBlock], thr[kPtBlock], m_nt[kPtBlock], s_nt[kPtBlock], m_all[kPtBlock], s_all[kPtBlock], ins[kPtBlock];
+  int f[kPtBlock];
+  const size_t at0 = (size_t)b.q * a.pts.stride + b.p0;
+  double* st = a.fields + at0 * kFields * C + b.c;
+  double* hp = a.heap + at0 * K * C + b.c;
 #pragma unroll
   for (int j = 0; j < kPtBlock; ++j) {
-    const int p = j < np ? p0 + j : p0;                            // a block's missing points repeat its first (never stored)
-    const size_t at = (size_t)q * ps + p;
-    lc[j] = LIK == kGiven ? 0.0 : a.pts.ln_conc[at];
-    yv[j] = LIK == kGiven ? 0.0 : a.pts.response[at];
-    tg[j] = LIK == kGiven ? 0 : clamp_tag(a.pts.tag[at], LIK == kHierarchical ? a.ne - 1 : 2);
     const double* sj = st + (size_t)j * kFields * C;
-    const bool load = !fresh && j < np;
-    thr[j] = load ? a.thr[at] : PHF_INF;
+    const bool load = !fresh && j < b.np;
+    thr[j] = load ? a.thr[at0 + j] : PHF_INF;
     m_nt[j] = load ? sj[0] : -PHF_INF;
     s_nt[j] = load ? sj[C] : 0.0;
     m_all[j] = load ? sj[2 * C] : -PHF_INF;
@@ -201,47 +182,14 @@ __global__ __launch_bounds__(kThreads) void psis_accumulate_kernel(const PsisArg
     ins[j] = load ? sj[5 * C] : 0.0;
     h[j] = f[j] > 0 ? hp[(size_t)j * K * C] : -PHF_INF;
   }
-  const size_t rstep = (size_t)a.Q * a.stride_cols * C;
-  const double* xr = a.rows + (size_t)q * a.stride_cols * C + c;
-  for (int64_t r = 0; r < a.nr; ++r) {
-    const double* x = xr + (size_t)r * rstep;
-    if (LIK == kGiven) {
-#pragma unroll
-      for (int j = 0; j < kPtBlock; ++j) {
-        if (j < np) {
-          const double l = x[(size_t)(p0 + j) * C];
-          lse_add(l, m_all[j], s_all[j], k_exp);
-          psis_take(l, thr[j], h[j], f[j], m_nt[j], s_nt[j], ins[j], hp + (size_t)j * K * C, C, K, k_exp);
-        }
-      }
-    } else if (LIK == kHierarchical) {
-      const phf_pw_sigma sg = phf_pw_sigma_terms(x[(size_t)(4 + 2 * a.ne) * C], k_log);
-#pragma unroll
-      for (int j = 0; j < kPtBlock; ++j) {
-        if (j < np) {
-          const double ln_ic50 = PHF_LN10 * (6.0 - x[(size_t)(4 + 2 * tg[j]) * C]);
-          const double l = phf_pw_hier_point(lc[j], yv[j], x[(size_t)(5 + 2 * tg[j]) * C], ln_ic50, sg, k_exp, k_log);
-          lse_add(l, m_all[j], s_all[j], k_exp);
-          psis_take(l, thr[j], h[j], f[j], m_nt[j], s_nt[j], ins[j], hp + (size_t)j * K * C, C, K, k_exp);
-        }
-      }
-    } else {
-      const double pic50 = x[0], hill = LIK == 2 ? x[C] : 1.0;
-      const double ln_ic50 = PHF_LN10 * (6.0 - pic50);
-      const phf_pw_sigma sg = phf_pw_sigma_terms(x[(size_t)LIK * C], k_log);
-#pragma unroll
-      for (int j = 0; j < kPtBlock; ++j) {
-        if (j < np) {
-          const double l = phf_pw_sl_point(LIK, lc[j], yv[j], tg[j], hill, ln_ic50, sg, k_exp);
-          lse_add(l, m_all[j], s_all[j], k_exp);
-          psis_take(l, thr[j], h[j], f[j], m_nt[j], s_nt[j], ins[j], hp + (size_t)j * K * C, C, K, k_exp);
-        }
-      }
-    }
-  }
+  for (int64_t r = 0; r < a.nr; ++r)
+    phf_point_block_row<LIK>(a, b, b.xr + (size_t)r * b.rstep, k_exp, k_log, [&](int j, double l) {
+      lse_add(l, m_all[j], s_all[j], k_exp);
+      psis_take(l, thr[j], h[j], f[j], m_nt[j], s_nt[j], ins[j], hp + (size_t)j * K * C, C, K, k_exp);
+    });
 #pragma unroll
   for (int j = 0; j < kPtBlock; ++j)
-    if (j < np) {
+    if (j < b.np) {
       double* sj = st + (size_t)j * kFields * C;
       sj[0] = m_nt[j]; sj[C] = s_nt[j]; sj[2 * C] = m_all[j]; sj[3 * C] = s_all[j]; sj[4 * C] = (double)f[j]; sj[5 * C] = ins[j];
     }
@@ -602,8 +550,6 @@ __global__ __launch_bounds__(kThreads) void psis_reduce_kernel(const PsisArgs a)
     __syncthreads();
   }
 }
-
-unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // the rows after which T is recomputed: fixed, so the launches are cut at the same rows however the calls cut the run
 int64_t next_threshold_row(int64_t r) {

@@ -1,15 +1,10 @@
 // phf_quantiles.hip — posterior quantiles and dose-response credible bands from exact-count histograms (include/pyhillfit_amd.h).
 //
-// Per slot (problem, column) — a column of the rows, or one dose of the Hill curve (curve bands) — the workspace keeps B bins of a
-// grid fixed by an anchor a (the first finite value, in (row, chain) order, of all rows accumulated), a power-of-two base width
-// w0 = 2^(floor(log2 max(|a|, 2^-30)) - 40) and a level k:
-//     t = (x - a) * (1/w0)          (1/w0 is a power of two: the same double as (x - a)/w0; -ffp-contract=off: no FMA anywhere)
-//     j = floor(t * 2^-k) + B/2     (t * 2^-k by ldexp: exact)
+// Per slot (problem, column) — a column of the rows, or one dose of the Hill curve (curve bands) — the workspace keeps B bins of the
+// grid of phf_grid.h: an anchor a (the first finite value, in (row, chain) order, of all rows accumulated), a power-of-two base width
+// w0 and a level k, t = (x - a) * (1/w0), j = floor(t * 2^-k) + B/2.
 // Each accumulate call runs
-//   prepare  one workgroup per slot: the anchor (first call with a finite value), a min/max pass over the call's values, then the
-//            least level k' >= k whose bins hold the running [min, max]; when k' > k the counts merge 2^(k'-k)-fold in place
-//            (floor(floor(y)/2^m) = floor(y/2^m): the final counts are those of binning every value at the final level, which is
-//            the least level holding the global [min, max] — the same however the rows are cut into calls);
+//   prepare  one workgroup per slot (phf_grid_prepare): anchor, min/max, the least level holding the running [min, max], the merge;
 //   bin      workgroups of (slot, slice of the call's values): a workgroup-private uint32 histogram in LDS (a wavefront whose lanes
 //            all fall in one bin adds once), flushed to the uint64 counts in HBM with integer atomics for its non-zero bins only.
 // Integer counts are order-independent: the result is bit-identical whatever the launch shape, the arrival order or the row cuts.
@@ -24,20 +19,19 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
+#include "phf_grid.h"
 #include "phf_hier_bands.h"
 #include "phf_pointwise.h"
 
 namespace {
 
-constexpr int kPrepThreads = 256;
+constexpr int kPrepThreads = kGridPrepThreads;
 constexpr int kBinThreads = 512;
 constexpr int kReduceThreads = 256;
-constexpr int kHdr = 8;                 // anchor, w0, min, max, level, anchored, 0, 0
-constexpr int kOutHead = 8;             // min, max, finite draws, non-finite, bin width, level, anchor, w0
+constexpr int kHdr = PHF_GRID_HDR;
+constexpr int kOutHead = kGridOutHead;
 constexpr int kOutPerProb = 4;          // value, lo, hi, bin
-constexpr int kMinBins = 64, kMaxBins = 32768, kMaxProbs = 64;
-constexpr int64_t kValuesPerBlock = 131072;   // values one bin workgroup takes before a call's slot is split over more
-constexpr int kTargetBlocks = 4096;           // ... up to about this many bin workgroups per launch
+constexpr int kMaxBins = 32768, kMaxProbs = 64;
 constexpr int64_t kMaxFlat = 0x7fffffff;      // rows x chains of one call: a 31-bit flat index
 constexpr int kUnderlying = 3, kFuture = 4;   // value sources after the column (0) and the single-level curves (1, 2)
 constexpr int kDrawThreads = 256;
@@ -85,13 +79,6 @@ __device__ inline double q_value(const QArgs& a, int q, int k, unsigned i, phf_k
   return phf_pw_pred(MODEL, a.ln_dose[(size_t)q * a.G + k], hill, PHF_LN10 * (6.0 - pic50), k_exp);
 }
 
-__device__ inline double q_t(double x, double anchor, double inv_w0) { return (x - anchor) * inv_w0; }
-
-// do the level-k bins hold [tmin, tmax]?
-__device__ inline bool q_holds(double tmin, double tmax, int k, int B) {
-  return __builtin_floor(__builtin_ldexp(tmin, -k)) >= -(double)(B / 2) && __builtin_floor(__builtin_ldexp(tmax, -k)) < (double)(B / 2);
-}
-
 // the 2^(j/64) table of phf_exp_* into LDS (the Hill curve needs no other table); the future experiment's draws take logarithms: the log table too
 template <int MODEL>
 __device__ inline void load_tables() {
@@ -117,96 +104,17 @@ __device__ inline void load_tables() {
   }                                                                 \
   const phf_ktab name = name##_buf
 
-// block reductions through a small LDS array (blockDim.x <= 1024: 16 wavefronts)
-__device__ inline double block_min(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v = __builtin_fmin(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x / 64] = v;
-  __syncthreads();
-  double r = sh[0];
-  for (int w = 1; w < (int)blockDim.x / 64; ++w) r = __builtin_fmin(r, sh[w]);
-  return r;
-}
-
-__device__ inline double block_max(double v, double* sh) { return -block_min(-v, sh); }
-
-__device__ inline unsigned block_min_u(unsigned v, unsigned* sh) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = __shfl_xor(v, o, 64);
-    v = u < v ? u : v;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x / 64] = v;
-  __syncthreads();
-  unsigned r = sh[0];
-  for (int w = 1; w < (int)blockDim.x / 64; ++w) r = sh[w] < r ? sh[w] : r;
-  return r;
-}
-
-// ---- prepare: anchor, min/max, level, merge ----------------------------------------------------------------------------------------
+// ---- prepare: anchor, min/max, level, merge (phf_grid.h) -----------------------------------------------------------------------------
 template <int MODEL>
 __global__ __launch_bounds__(kPrepThreads) void q_prepare_kernel(const QArgs a) {
   extern __shared__ unsigned long long s_merge[];              // [B/2]
-  __shared__ double s_red[16];
-  __shared__ unsigned s_redu[16];
-  __shared__ int s_level[2];
   load_tables<MODEL>();
   PHF_KFETCH_V(k_exp, phf_k_exp, PHF_K_EXP_N);
   Q_KFETCH_LOG(k_log);
   const int q = blockIdx.x / a.count, k = blockIdx.x % a.count;
   const size_t s = (size_t)q * a.spp + a.first + k;
-  double* h = a.hdr + s * kHdr;
-  const int tid = threadIdx.x;
-  if (h[5] == 0.0) {                                           // not anchored yet: the first finite value in (row, chain) order
-    unsigned best = 0xffffffffu;
-    for (unsigned i = tid; i < a.n; i += kPrepThreads)
-      if (__builtin_isfinite(q_value<MODEL>(a, q, k, i, k_exp, k_log))) { best = i; break; }
-    best = block_min_u(best, s_redu);
-    if (best == 0xffffffffu) return;                           // nothing finite yet: the bin pass counts every value apart
-    if (tid == 0) {
-      const double x = q_value<MODEL>(a, q, k, best, k_exp, k_log);
-      const double m = __builtin_fmax(__builtin_fabs(x), 0x1p-30);
-      h[0] = x;
-      h[1] = __builtin_ldexp(1.0, __builtin_amdgcn_frexp_exp(m) - 41);   // frexp exponent - 1 = floor(log2 m)
-      h[2] = x; h[3] = x; h[4] = 0.0; h[5] = 1.0;
-    }
-    __syncthreads();
-  }
-  const double anchor = h[0], inv_w0 = 1.0 / h[1];             // a power of two: exact
-  double lo = PHF_INF, hi = -PHF_INF;
-  for (unsigned i = tid; i < a.n; i += kPrepThreads) {
-    const double x = q_value<MODEL>(a, q, k, i, k_exp, k_log);
-    if (__builtin_isfinite(q_t(x, anchor, inv_w0))) { lo = __builtin_fmin(lo, x); hi = __builtin_fmax(hi, x); }
-  }
-  lo = block_min(lo, s_red);
-  hi = block_max(hi, s_red);
-  if (tid == 0) {
-    const double mn = __builtin_fmin(h[2], lo), mx = __builtin_fmax(h[3], hi);
-    const int k0 = (int)h[4];
-    int k1 = k0;
-    const double tmin = q_t(mn, anchor, inv_w0), tmax = q_t(mx, anchor, inv_w0);
-    while (!q_holds(tmin, tmax, k1, a.B) && k1 < 1100) ++k1;
-    h[2] = mn; h[3] = mx; h[4] = (double)k1;
-    s_level[0] = k0; s_level[1] = k1;
-  }
-  __syncthreads();
-  const int k0 = s_level[0], k1 = s_level[1];
-  if (k1 == k0) return;
-  // merge: new bin of old j = ((j - B/2) >> D) + B/2 (an arithmetic shift is floor division); D >= log2 B acts as log2 B
-  int log2B = 0;
-  while ((1 << log2B) < a.B) ++log2B;
-  const int D = k1 - k0 < log2B ? k1 - k0 : log2B;
-  const int half = a.B / 2;
-  const int nlo = half + ((-half) >> D), nn = half + ((half - 1) >> D) - nlo + 1;   // nn <= B/2
-  for (int i = tid; i < nn; i += kPrepThreads) s_merge[i] = 0ull;
-  __syncthreads();
-  unsigned long long* cnt = a.counts + s * a.B;
-  for (int j = tid; j < a.B; j += kPrepThreads) {
-    const unsigned long long c = cnt[j];
-    if (c) atomicAdd(&s_merge[((j - half) >> D) + half - nlo], c);
-  }
-  __syncthreads();
-  for (int j = tid; j < a.B; j += kPrepThreads) cnt[j] = (j >= nlo && j < nlo + nn) ? s_merge[j - nlo] : 0ull;
+  phf_grid_prepare<1>(a.hdr + s * kHdr, a.counts + s * a.B, a.B, a.n, s_merge,
+                      [&](unsigned i) { return q_value<MODEL>(a, q, k, i, k_exp, k_log); });
 }
 
 // ---- bin: LDS histogram per workgroup, flushed with integer atomics ----------------------------------------------------------------
@@ -220,10 +128,7 @@ __global__ __launch_bounds__(kBinThreads) void q_bin_kernel(const QArgs a) {
   const int slot = blockIdx.x / a.splits;
   const int q = slot / a.count, k = slot % a.count;
   const size_t s = (size_t)q * a.spp + a.first + k;
-  const double* h = a.hdr + s * kHdr;
-  const bool anchored = h[5] != 0.0;
-  const double anchor = h[0], inv_w0 = 1.0 / h[1];
-  const int level = (int)h[4], half = a.B / 2;
+  const phf_grid_view grid = phf_grid_load(a.hdr + s * kHdr);
   const int tid = threadIdx.x;
   for (int j = tid; j < a.B; j += kBinThreads) s_hist[j] = 0u;
   __syncthreads();
@@ -233,14 +138,7 @@ __global__ __launch_bounds__(kBinThreads) void q_bin_kernel(const QArgs a) {
   const int lane = __lane_id();
   for (unsigned i = i0 + tid; i < i1; i += kBinThreads) {
     const double x = q_value<MODEL>(a, q, k, i, k_exp, k_log);
-    int j = -1;
-    if (anchored) {
-      const double t = q_t(x, anchor, inv_w0);
-      if (__builtin_isfinite(t)) {
-        const double f = __builtin_floor(__builtin_ldexp(t, -level)) + (double)half;
-        j = (int)__builtin_fmin(__builtin_fmax(f, 0.0), (double)(a.B - 1));   // the level holds [min, max]: the clamp is a guard
-      }
-    }
+    const int j = phf_grid_index(grid, x, a.B);
     nf += j < 0;
     const unsigned long long active = __ballot(1);
     const int j0 = __builtin_amdgcn_readfirstlane(j);
@@ -280,15 +178,7 @@ __global__ __launch_bounds__(kReduceThreads) void q_reduce_kernel(const QReduceA
       s_sum[t] = run;
       run += v;
     }
-    const bool anchored = h[5] != 0.0;
-    o[0] = anchored ? h[2] : PHF_NAN;
-    o[1] = anchored ? h[3] : PHF_NAN;
-    o[2] = (double)run;
-    o[3] = (double)a.nonfinite[s];
-    o[4] = anchored ? __builtin_ldexp(h[1], (int)h[4]) : PHF_NAN;
-    o[5] = h[4];
-    o[6] = anchored ? h[0] : PHF_NAN;
-    o[7] = anchored ? h[1] : PHF_NAN;
+    phf_grid_write_head(h, run, a.nonfinite[s], o);
     for (int p = 0; p < a.P; ++p)
       for (int f = 0; f < kOutPerProb; ++f) o[kOutHead + kOutPerProb * p + f] = PHF_NAN;
   }
@@ -296,7 +186,8 @@ __global__ __launch_bounds__(kReduceThreads) void q_reduce_kernel(const QReduceA
   const unsigned long long before = s_sum[tid];
   const double N = o[2];
   if (N == 0.0 || tid >= used) return;
-  const double mn = h[2], mx = h[3], width = __builtin_ldexp(h[1], (int)h[4]), anchor = h[0];
+  const double mn = h[PHF_GRID_MIN], mx = h[PHF_GRID_MAX], width = __builtin_ldexp(h[PHF_GRID_W0], (int)h[PHF_GRID_LEVEL]);
+  const double anchor = h[PHF_GRID_ANCHOR];
   const int half = a.B / 2;
   for (int p = 0; p < a.P; ++p) {
     double r = __builtin_ceil(a.probs[p] * N);
@@ -355,10 +246,7 @@ int check_geometry(const char* who, int num_problems, int num_columns, int curve
     std::snprintf(msg, sizeof msg, "%s: num_problems must be positive, num_columns and curve_points non-negative, not both 0", who);
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
   }
-  if (bins < kMinBins || bins > kMaxBins || (bins & (bins - 1)) != 0) {
-    std::snprintf(msg, sizeof msg, "%s: bins must be a power of two in [%d, %d] (got %d)", who, kMinBins, kMaxBins, bins);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (phf_grid_check_bins(who, bins, kMaxBins) != PHF_OK) return PHF_ERR_INVALID_ARGUMENT;
   if ((double)num_problems * (num_columns + curve_points) > 2147483647.0 / 8) {
     std::snprintf(msg, sizeof msg, "%s: too many slots (fewer problems per workspace)", who);
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
@@ -405,22 +293,12 @@ int check_rows(const char* who, const double* rows, int64_t num_rows, int row_st
   return PHF_OK;
 }
 
-template <typename K>
-int allow_lds(K kernel, size_t bytes, const char* who) {
-  if (bytes <= 65536) return PHF_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return phf_check_launch(who);
-  return PHF_OK;
-}
-
 template <int MODEL>
 int launch(QArgs a, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int slots = a.Q * a.count;
-  const int64_t want = (a.n + kValuesPerBlock - 1) / kValuesPerBlock;
-  const int64_t room = kTargetBlocks / slots > 1 ? kTargetBlocks / slots : 1;
-  a.splits = (int)(want < room ? (want > 0 ? want : 1) : room);
-  a.per_split = (unsigned)((a.n + a.splits - 1) / a.splits);
+  const phf_grid_split split = phf_grid_split_of(a.n, slots);
+  a.splits = split.splits; a.per_split = split.per_split;
   const size_t merge_lds = (size_t)a.B / 2 * 8, hist_lds = (size_t)a.B * 4;
   int rc;
   if ((rc = allow_lds(q_prepare_kernel<MODEL>, merge_lds, "hipFuncSetAttribute(q_prepare_kernel)")) != PHF_OK) return rc;

@@ -13,6 +13,7 @@
 #ifndef PHF_SENSITIVITY_H
 #define PHF_SENSITIVITY_H
 
+#include "phf_grid.h"
 #include "phf_hier_model.h"
 #include "phf_math.h"
 #include "phf_model.h"
@@ -113,8 +114,8 @@ PHF_HD void phf_sens_column_step(double w, double d, int valid, double* cw, doub
   }
 }
 
-/* the quantiles' rule: a value is binned when its grid coordinate is finite */
-PHF_HD int phf_sens_binned(double x, double anchor, double inv_w0) { return __builtin_isfinite((x - anchor) * inv_w0); }
+/* the histogram bins this value (phf_grid.h) */
+PHF_HD int phf_sens_binned(double x, double anchor, double inv_w0) { return phf_grid_binned(x, anchor, inv_w0); }
 
 /* ---- cumulative Jensen-Shannon sums ----------------------------------------------------------------------------------------------
  * P log2(2P / (P + Q)) + Q log2(2Q / (P + Q)), 0 log 0 = 0 */

@@ -1,9 +1,9 @@
 // phf_sensitivity.hip — power-scaling sensitivity of prior and likelihood, streamed over the samplers' rows (include/pyhillfit_amd.h;
 // phf_sensitivity.h holds the arithmetic, shared with the host build the tests compare against).
 //
-// Per (problem, column) slot the workspace keeps, on ONE grid (the quantiles' rule: anchor = the first finite value in (row, chain)
-// order, w0 = 2^(floor(log2 max(|a|, 2^-30)) - 40), the least level holding [min, max], 2^dk-fold merges), five uint64 arrays of B
-// bins: the base counts and the integer masses m = floor(w 2^20 + 1/2) of the four (component, direction) weights.  Integer sums do not
+// Per (problem, column) slot the workspace keeps, on ONE grid (phf_grid.h, the grid the quantiles bin on: the base counts here are
+// the quantiles' counts), five uint64 arrays of B bins:
+// the base counts and the integer masses m = floor(w 2^20 + 1/2) of the four (component, direction) weights.  Integer sums do not
 // depend on the order: the arrays are identical however the rows arrive or are cut into calls.  Per (problem, component) c_ref is the
 // first finite component in (row, chain) order of all rows accumulated.  Per (problem, component, direction, chain) sum w, sum w^2 and
 // the clamped count, and per column sum w, sum w d, sum w d^2 (d = x - the slot's anchor), are owned by one lane in row order.
@@ -23,29 +23,30 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
+#include "phf_grid.h"
 #include "phf_sensitivity.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kPrepThreads = 256;
+constexpr int kPrepThreads = kGridPrepThreads;
 constexpr int kBinThreads = 512;
-constexpr int kHdr = 8;                       // anchor, w0, min, max, level, anchored, 0, 0
+constexpr int kHdr = PHF_GRID_HDR;
 constexpr int kArrays = 5;                    // base counts, then the masses of prior down / up, likelihood down / up
 constexpr int kWeights = 4;
 constexpr int kDraw = 6;                      // scratch doubles per draw: the two components, the four weights
 constexpr int kWFields = 4;                   // per (weight, chain): n, sum w, sum w^2, clamped
 constexpr int kCFields = 3;                   // per (column, array, chain): sum w, sum w d, sum w d^2
-constexpr int kSlotHead = 8;                  // min, max, binned draws, non-finite, bin width, level, anchor, w0
+constexpr int kSlotHead = kGridOutHead;
 constexpr int kSlotPerWeight = 5;             // numerator and denominator on the CDF, on the survival function, the total mass
 constexpr int kSlotOut = kSlotHead + kWeights * kSlotPerWeight;
 constexpr int kColOut = 4;                    // merged sum w, sum w d, sum w d^2; between-chain standard error of the mean shift (in d)
-constexpr int kMinBins = 64, kMaxBins = 4096; // 36 bytes of LDS per bin in the bin kernel: 4 096 bins are 144 KiB of a CU's 160
+constexpr int kMaxBins = 4096;                // 36 bytes of LDS per bin in the bin kernel: 4 096 bins are 144 KiB of a CU's 160
 constexpr size_t kScratchTarget = (size_t)256 << 20;   // the scratch region: about this many bytes ...
 constexpr int64_t kMinBlockRows = 16;                  // ... but at least this many rows (or all of them)
-constexpr int64_t kValuesPerBlock = 131072;
-constexpr int kTargetBlocks = 4096;
+// `kind` of phf_sensitivity_accumulate: which evaluator gives the two components.  Not the `likelihood` codes of phf_point_block.h
+// (kHierarchical, kGiven), which this file does not include: another entry point's argument, with values that happen to agree
 constexpr int kSingle1 = 1, kSingle2 = 2, kHier = 3, kGiven = 4;
 
 struct Layout {
@@ -173,32 +174,6 @@ __global__ __launch_bounds__(kThreads) void sens_batch_kernel(const phf_points s
   out[2 * m + i] = pop;
 }
 
-// ---- block reductions (blockDim.x <= 1024) -------------------------------------------------------------------------------------------
-__device__ inline double block_min(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v = __builtin_fmin(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x / 64] = v;
-  __syncthreads();
-  double r = sh[0];
-  for (int w = 1; w < (int)blockDim.x / 64; ++w) r = __builtin_fmin(r, sh[w]);
-  return r;
-}
-
-__device__ inline double block_max(double v, double* sh) { return -block_min(-v, sh); }
-
-__device__ inline unsigned block_min_u(unsigned v, unsigned* sh) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = __shfl_xor(v, o, 64);
-    v = u < v ? u : v;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x / 64] = v;
-  __syncthreads();
-  unsigned r = sh[0];
-  for (int w = 1; w < (int)blockDim.x / 64; ++w) r = sh[w] < r ? sh[w] : r;
-  return r;
-}
-
 // scratch double f of draw i (= row * C + chain) of problem q
 __device__ inline double* draw_at(const SArgs& a, int q, unsigned i, int f) {
   const unsigned r = i / (unsigned)a.C, c = i - r * (unsigned)a.C;
@@ -262,77 +237,18 @@ __global__ __launch_bounds__(kThreads) void sens_weights_kernel(const SArgs a) {
     for (int f = 0; f < kWFields; ++f) st[((size_t)k * kWFields + f) * C] = acc[k][f];
 }
 
-// ---- prepare: anchor, min/max, level, merge of the five arrays (the quantiles' rule) --------------------------------------------------
+// ---- prepare: anchor, min/max, level, merge of the five arrays (phf_grid.h) -----------------------------------------------------------
 __device__ inline double col_value(const SArgs& a, int q, int j, unsigned i) {
   const unsigned r = i / (unsigned)a.C, c = i - r * (unsigned)a.C;
   return a.rows[(((size_t)r * a.Q + q) * a.stride + j) * (size_t)a.C + c];
 }
 
-__device__ inline bool holds(double tmin, double tmax, int k, int B) {
-  return __builtin_floor(__builtin_ldexp(tmin, -k)) >= -(double)(B / 2) && __builtin_floor(__builtin_ldexp(tmax, -k)) < (double)(B / 2);
-}
-
 __global__ __launch_bounds__(kPrepThreads) void sens_prepare_kernel(const SArgs a) {
   extern __shared__ unsigned long long s_merge[];              // [B/2]
-  __shared__ double s_red[16];
-  __shared__ unsigned s_redu[16];
-  __shared__ int s_level[2];
   const int q = blockIdx.x / a.ncol, j = blockIdx.x % a.ncol;
   const size_t s = blockIdx.x;
-  double* h = a.hdr + s * kHdr;
-  const int tid = threadIdx.x;
-  if (h[5] == 0.0) {                                           // not anchored yet: the first finite value in (row, chain) order
-    unsigned best = 0xffffffffu;
-    for (unsigned i = tid; i < a.n; i += kPrepThreads)
-      if (__builtin_isfinite(col_value(a, q, j, i))) { best = i; break; }
-    best = block_min_u(best, s_redu);
-    if (best == 0xffffffffu) return;
-    if (tid == 0) {
-      const double x = col_value(a, q, j, best);
-      const double m = __builtin_fmax(__builtin_fabs(x), 0x1p-30);
-      h[0] = x;
-      h[1] = __builtin_ldexp(1.0, __builtin_amdgcn_frexp_exp(m) - 41);
-      h[2] = x; h[3] = x; h[4] = 0.0; h[5] = 1.0;
-    }
-    __syncthreads();
-  }
-  const double anchor = h[0], inv_w0 = 1.0 / h[1];             // a power of two: exact
-  double lo = PHF_INF, hi = -PHF_INF;
-  for (unsigned i = tid; i < a.n; i += kPrepThreads) {
-    const double x = col_value(a, q, j, i);
-    if (phf_sens_binned(x, anchor, inv_w0)) { lo = __builtin_fmin(lo, x); hi = __builtin_fmax(hi, x); }
-  }
-  lo = block_min(lo, s_red);
-  hi = block_max(hi, s_red);
-  if (tid == 0) {
-    const double mn = __builtin_fmin(h[2], lo), mx = __builtin_fmax(h[3], hi);
-    const int k0 = (int)h[4];
-    int k1 = k0;
-    const double tmin = (mn - anchor) * inv_w0, tmax = (mx - anchor) * inv_w0;
-    while (!holds(tmin, tmax, k1, a.B) && k1 < 1100) ++k1;
-    h[2] = mn; h[3] = mx; h[4] = (double)k1;
-    s_level[0] = k0; s_level[1] = k1;
-  }
-  __syncthreads();
-  const int k0 = s_level[0], k1 = s_level[1];
-  if (k1 == k0) return;
-  int log2B = 0;
-  while ((1 << log2B) < a.B) ++log2B;
-  const int D = k1 - k0 < log2B ? k1 - k0 : log2B;
-  const int half = a.B / 2;
-  const int nlo = half + ((-half) >> D), nn = half + ((half - 1) >> D) - nlo + 1;   // nn <= B/2
-  for (int arr = 0; arr < kArrays; ++arr) {
-    for (int i = tid; i < nn; i += kPrepThreads) s_merge[i] = 0ull;
-    __syncthreads();
-    unsigned long long* cnt = a.counts + (s * kArrays + arr) * a.B;
-    for (int b = tid; b < a.B; b += kPrepThreads) {
-      const unsigned long long v = cnt[b];
-      if (v) atomicAdd(&s_merge[((b - half) >> D) + half - nlo], v);
-    }
-    __syncthreads();
-    for (int b = tid; b < a.B; b += kPrepThreads) cnt[b] = (b >= nlo && b < nlo + nn) ? s_merge[b - nlo] : 0ull;
-    __syncthreads();
-  }
+  phf_grid_prepare<kArrays>(a.hdr + s * kHdr, a.counts + s * kArrays * a.B, a.B, a.n, s_merge,
+                            [&](unsigned i) { return col_value(a, q, j, i); });
 }
 
 // ---- columns: a chain's sums of one column under the base and the four weights -------------------------------------------------------
@@ -344,8 +260,8 @@ __global__ __launch_bounds__(kThreads) void sens_columns_kernel(const SArgs a) {
   const int c = cg * 64 + (threadIdx.x & 63);
   if (c >= a.C) return;
   const double* h = a.hdr + (size_t)slot * kHdr;
-  if (h[5] == 0.0) return;                                      // no finite value of this column yet: nothing enters
-  const double anchor = h[0], inv_w0 = 1.0 / h[1];
+  if (h[PHF_GRID_ANCHORED] == 0.0) return;                      // no finite value of this column yet: nothing enters
+  const double anchor = h[PHF_GRID_ANCHOR], inv_w0 = 1.0 / h[PHF_GRID_W0];
   const size_t C = (size_t)a.C;
   double* st = a.csum + (size_t)slot * kArrays * kCFields * C + c;
   double acc[kArrays][kCFields];
@@ -378,10 +294,7 @@ __global__ __launch_bounds__(kBinThreads) void sens_bin_kernel(const SArgs a) {
   const int split = blockIdx.x % a.splits;
   const int slot = blockIdx.x / a.splits;
   const int q = slot / a.ncol, j = slot % a.ncol;
-  const double* h = a.hdr + (size_t)slot * kHdr;
-  const bool anchored = h[5] != 0.0;
-  const double anchor = h[0], inv_w0 = 1.0 / h[1];
-  const int level = (int)h[4], half = a.B / 2;
+  const phf_grid_view grid = phf_grid_load(a.hdr + (size_t)slot * kHdr);
   const int tid = threadIdx.x;
   for (int b = tid; b < a.B; b += kBinThreads) s_hist[b] = 0u;
   for (int b = tid; b < kWeights * a.B; b += kBinThreads) s_mass[b] = 0ull;
@@ -391,14 +304,7 @@ __global__ __launch_bounds__(kBinThreads) void sens_bin_kernel(const SArgs a) {
   unsigned nf = 0;
   for (unsigned i = i0 + tid; i < i1; i += kBinThreads) {
     const double x = col_value(a, q, j, i);
-    int b = -1;
-    if (anchored) {
-      const double t = (x - anchor) * inv_w0;
-      if (__builtin_isfinite(t)) {
-        const double f = __builtin_floor(__builtin_ldexp(t, -level)) + (double)half;
-        b = (int)__builtin_fmin(__builtin_fmax(f, 0.0), (double)(a.B - 1));   // the level holds [min, max]: the clamp is a guard
-      }
-    }
+    const int b = phf_grid_index(grid, x, a.B);
     nf += b < 0;
     if (b >= 0) {
       atomicAdd(&s_hist[b], 1u);
@@ -454,18 +360,9 @@ __global__ __launch_bounds__(kThreads) void sens_reduce_cjs_kernel(const RArgs a
 #pragma unroll
   for (int f = 0; f < kSlotPerWeight; ++f) o[kSlotHead + k * kSlotPerWeight + f] = r[f];
   if (k == 0) {
-    const double* h = a.hdr + (size_t)s * kHdr;
-    const bool anchored = h[5] != 0.0;
     unsigned long long n = 0;
     for (int b = 0; b < a.B; ++b) n += base[b];
-    o[0] = anchored ? h[2] : PHF_NAN;
-    o[1] = anchored ? h[3] : PHF_NAN;
-    o[2] = (double)n;
-    o[3] = (double)a.nonfinite[s];
-    o[4] = anchored ? __builtin_ldexp(h[1], (int)h[4]) : PHF_NAN;
-    o[5] = h[4];
-    o[6] = anchored ? h[0] : PHF_NAN;
-    o[7] = anchored ? h[1] : PHF_NAN;
+    phf_grid_write_head(a.hdr + (size_t)s * kHdr, n, a.nonfinite[s], o);
   }
 }
 
@@ -510,8 +407,6 @@ __global__ __launch_bounds__(kThreads) void sens_reduce_sums_kernel(const RArgs 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
-unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 int fail(const char* who, const char* what) {
   char msg[kPhfErrorBufferSize];
   std::snprintf(msg, sizeof msg, "%s: %s", who, what);
@@ -519,13 +414,9 @@ int fail(const char* who, const char* what) {
 }
 
 int check_geometry(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows, int bins) {
-  char msg[kPhfErrorBufferSize];
   if (num_problems < 1 || num_columns < 1 || num_chains < 1) return fail(who, "num_problems, num_columns and num_chains must be positive");
   if (total_rows < 1) return fail(who, "total_rows must be positive");
-  if (bins < kMinBins || bins > kMaxBins || (bins & (bins - 1)) != 0) {
-    std::snprintf(msg, sizeof msg, "%s: bins must be a power of two in [%d, %d] (got %d)", who, kMinBins, kMaxBins, bins);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (phf_grid_check_bins(who, bins, kMaxBins) != PHF_OK) return PHF_ERR_INVALID_ARGUMENT;
   if ((double)total_rows * num_chains > 4294967296.0) return fail(who, "total_rows x num_chains must not exceed 2^32 draws (the masses' uint64 sums)");
   if ((double)num_problems * num_columns * ((num_chains + 63) / 64) > 2147483647.0 / 8 || (double)num_problems * kDraw * num_chains * 8 > 1e12)
     return fail(who, "launch grid too large (fewer problems per workspace)");
@@ -533,14 +424,6 @@ int check_geometry(const char* who, int num_problems, int num_columns, int num_c
 }
 
 bool delta_ok(double delta) { return delta > 0.0 && delta <= 0.25; }
-
-template <typename K>
-int allow_lds(K kernel, size_t bytes, const char* who) {
-  if (bytes <= 65536) return PHF_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return phf_check_launch(who);
-  return PHF_OK;
-}
 
 int check_sl_points(const char* who, const phf_points* p, int num_problems) {
   if (!p || !p->ln_conc || !p->response || !p->weight || !p->counts || !p->pi_bit || !p->extra) return fail(who, "null single-level points");
@@ -653,10 +536,8 @@ extern "C" int phf_sensitivity_accumulate(int kind, const phf_points* sl_points,
     c.units = slots * a.ncg;
     hipLaunchKernelGGL(sens_columns_kernel, dim3(blocks_for(c.units, kWaves)), dim3(kThreads), 0, st, c);
     if ((rc = phf_check_launch("sens_columns_kernel")) != PHF_OK) return rc;
-    const int64_t want = (a.n + kValuesPerBlock - 1) / kValuesPerBlock;
-    const int64_t room = kTargetBlocks / slots > 1 ? kTargetBlocks / slots : 1;
-    a.splits = (int)(want < room ? (want > 0 ? want : 1) : room);
-    a.per_split = (unsigned)((a.n + a.splits - 1) / a.splits);
+    const phf_grid_split split = phf_grid_split_of(a.n, slots);
+    a.splits = split.splits; a.per_split = split.per_split;
     hipLaunchKernelGGL(sens_bin_kernel, dim3((unsigned)slots * a.splits), dim3(kBinThreads), bin_lds, st, a);
     if ((rc = phf_check_launch("sens_bin_kernel")) != PHF_OK) return rc;
   }

@@ -20,6 +20,7 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_common.h"
+#include "phf_device_util.h"
 #include "phf_model.h"
 
 namespace {
@@ -208,8 +209,6 @@ __global__ __launch_bounds__(kThreads) void ss_reduce_joint_kernel(const SsArgs 
   }
   if (lane == 0) a.out[p] = a.C > 1 ? sqrt(part.m2 / (part.n - 1.0)) / sqrt((double)a.C) : PHF_NAN;
 }
-
-unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 int check_shape(const char* who, int num_problems, int num_chains, int64_t total_rows) {
   char msg[kPhfErrorBufferSize];

@@ -250,6 +250,71 @@ def test_known_answer_through_the_device(gpu, shim):
     assert np.all(res["clamped"] == 0) and np.all(res["non_finite"] == 0)
 
 
+# ---- one grid, two users ----------------------------------------------------------------------------------------------------------
+GRID_ROWS, GRID_CUTS = 36, ((36,), (5, 17, 14))
+
+
+def grid_rows(Cn):
+    """[36][2][5][Cn]: three parameter columns — a constant, a normal with NaN and +-inf sprinkled in, one whose range grows 2^20-fold
+    from row 5 on (the second cut of (5, 17, 14)) — and two finite columns, the given components"""
+    rng = np.random.default_rng(100 + Cn)
+    x = np.empty((GRID_ROWS, 2, 5, Cn))
+    x[:, :, 0] = np.array([7.25, -0.003])[None, :, None]
+    x[:, :, 1] = rng.normal(-2.0, 0.7, (GRID_ROWS, 2, Cn))
+    x[0, 1, 1, 0] = np.nan                                      # problem 1's first value: a later one anchors the grid
+    x[2, 0, 1, 1], x[5, 0, 1, Cn - 1], x[20, 1, 1, 3], x[35, 0, 1, 0] = np.inf, -np.inf, np.nan, np.inf
+    x[:, :, 2] = 3.0 + rng.normal(0.0, 1e-4, (GRID_ROWS, 2, Cn))
+    x[5:, :, 2] = (x[5:, :, 2] - 3.0) * 2.0 ** 20 + 3.0
+    x[:, :, 3] = rng.normal(0.0, 16.0, (GRID_ROWS, 2, Cn)); x[:, :, 4] = rng.normal(-40.0, 6.0, (GRID_ROWS, 2, Cn))
+    return x
+
+
+def grid_state(obj, arrays):
+    """(base counts [Q][cols][B], header [Q][cols][8] as bit patterns, non-finite counts [Q][cols]) of a workspace that starts with
+    [slots][arrays][B] uint64 counts, [slots][8] header doubles and [slots] uint64 non-finite counts"""
+    S = obj.Q * obj.cols
+    raw = obj.ws.view(torch.int64).cpu().numpy().view(np.uint64)
+    n = S * arrays * obj.B
+    return (raw[:n].reshape(obj.Q, obj.cols, arrays, obj.B)[:, :, 0], raw[n:n + 8 * S].reshape(obj.Q, obj.cols, 8),
+            raw[n + 8 * S:n + 9 * S].reshape(obj.Q, obj.cols))
+
+
+@pytest.mark.parametrize("bins", [64, 4096])
+@pytest.mark.parametrize("Cn", [5, 96])
+def test_quantiles_and_sensitivity_share_one_grid(gpu, Cn, bins):
+    """the same rows through phf_quantiles_accumulate and through phf_sensitivity_accumulate (kind "given"): per slot the base counts,
+    the eight header doubles and the non-finite count are equal as integers and bit patterns, and the same however the rows are cut"""
+    from pyhillfit_amd.quantiles import PosteriorQuantiles
+    x = grid_rows(Cn)
+    t = torch.from_numpy(x).to(gpu)
+    states = []
+    for cuts in GRID_CUTS:
+        qn = PosteriorQuantiles(2, Cn, 3, GRID_ROWS, bins=bins, device=gpu)
+        r0 = 0
+        for n in cuts:
+            qn.accumulate(t[r0:r0 + n].contiguous())
+            r0 += n
+        ps = feed(x, cuts, "given", None, gpu, bins=bins, cols=3, given=(3, 4))
+        q_counts, q_nf = qn.counts()
+        q_state, s_state = grid_state(qn, 1), grid_state(ps, 5)
+        assert np.array_equal(q_state[0], q_counts) and np.array_equal(q_state[2], q_nf)     # the accessors read the same words
+        assert np.array_equal(s_state[0], ps.counts()[:, :, 0])
+        for got, want in zip(s_state, q_state):
+            assert got.dtype == np.uint64 and np.array_equal(got, want), cuts
+        states.append(q_state)
+    for a, b in zip(*states):
+        assert np.array_equal(a, b)
+    counts, hdr, nf = states[0]
+    level = hdr.view(np.float64)[:, :, 4]
+    assert np.all(counts.sum(axis=2) + nf == GRID_ROWS * Cn) and list(nf[:, 1]) == [3, 2] and np.all(nf[:, [0, 2]] == 0)
+    assert np.all((counts[:, 0] != 0).sum(axis=1) == 1) and np.all(level[:, 0] == 0)          # the constant: one bin, level 0
+    # the third column's level after the first cut alone: the second cut raises it by more than log2 B, the merge's D clamp
+    first = PosteriorQuantiles(2, Cn, 3, GRID_ROWS, bins=bins, device=gpu)
+    first.accumulate(t[:5].contiguous())
+    level5 = grid_state(first, 1)[1].view(np.float64)[:, :, 4]
+    assert np.all(level[:, 2] > level5[:, 2] + np.log2(bins))
+
+
 # ---- command lines --------------------------------------------------------------------------------------------------------------
 def _strip(s):
     s.pop("mh_samples_per_second")
