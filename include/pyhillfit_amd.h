@@ -772,6 +772,31 @@ int phf_sensitivity_reduce(int num_problems, int num_columns, int num_chains, in
 int phf_sensitivity_components(int kind, const phf_points* sl_points, const phf_hier_points* hier_points, const phf_hier_prior* prior,
                                int64_t m, const int32_t* problem_index, const double* theta, double* out, void* stream);
 
+/* ---- expected information gain of a next dose ---------------------------------------------------------------------------------
+ * (pyhillfit_amd/csrc/phf_design.hip, phf_design.h; DESIGN.md §3, "Next dose"; Lindley 1956, Chaloner & Verdinelli 1995).  For the
+ * single-level models (model 1 | 2, theta = columns 0..model of a row) and num_doses candidate doses per problem, the sums over the
+ * draws of what the mutual information between one further response at the dose and the parameters needs, the response being
+ * recorded to a resolution of 100/bins % block: the bins + 2 category masses of the censored normal (point masses at 0 and 100, bins
+ * equal bins of (0, 100)), the entropy of the draw's masses, and the entropy over the partition that merges adjacent bin pairs.
+ *   bins          128, 256, 512 or 1024
+ *   rows          device [num_rows][num_problems][row_stride_cols][num_chains], rows[0] being global post-burn-in row first_row;
+ *                 exactly the global rows r with r mod every == 0 are used, however the calls cut the rows
+ *   ln_doses      device [num_problems][num_doses] doubles: the natural logarithm of the candidate doses (uM)
+ *   num_slots     even, 2..64: chain c goes to accumulator slot c mod num_slots (so a slot's chains share the parity c & 1)
+ *   accumulators  device [num_problems][num_doses][num_slots][phf_design_accumulator_doubles(bins)] doubles, zeroed by the caller
+ *                 before the first call and updated in place: the mass at 0, the bins' masses, the mass at 100, per lane the sum of
+ *                 the fine entropies' shares [64] and of the coarse ones [64], the draws used, the draws skipped (phf_design.h)
+ * A draw with sigma <= 1e-3 or a parameter that is not finite is skipped and counted.  Every sum is a plain left-to-right sum over the
+ * slot's draws in (row, chain) order that starts from the stored value: the same rows and the same `every` give the same bits
+ * however the calls cut them, bit-identical to the host build of phf_design.h.  No atomics.  A call that holds no used row launches
+ * nothing.  Every argument is checked before any launch: PHF_ERR_INVALID_ARGUMENT without touching a GPU (phf_last_error() says why). */
+int phf_design_accumulator_doubles(int bins);   /* -1 for a bin count that is not allowed */
+/* the number of rows r in [first_row, first_row + num_rows) with r mod every == 0 (-1 for an invalid argument) */
+int64_t phf_design_rows_used(int64_t first_row, int64_t num_rows, int every);
+int phf_design_accumulate(int model, int bins, const double* rows, int64_t num_rows, int num_problems, int row_stride_cols,
+                          int num_chains, int64_t first_row, int every, const double* ln_doses, int num_doses, int num_slots,
+                          double* accumulators, size_t accumulator_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

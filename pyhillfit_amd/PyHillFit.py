@@ -9,6 +9,7 @@
            [--hierarchical --leave-experiment-out [--marginal-nodes 128] [--marginal-every T]]
            [--sensitivity [--sensitivity-delta 0.01] [--sensitivity-bins 4096] [--sensitivity-threshold 0.05]]
            [--hierarchical --de-every K [--de-population 64] [--de-gamma GAMMA] [--de-jump-every 10]]
+           [--next-dose G [--next-dose-concs c1,c2,...] [--next-dose-bins 256] [--next-dose-every 17]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -27,7 +28,8 @@ predicted future experiment at G doses (and at the named --band-concs), accumula
 --leave-experiment-out, the integrated leave-one-experiment-out cross-validation of every pair (pyhillfit_amd/marginal.py: each experiment's
 (Hill_i, pIC50_i) integrated out on the GPU, PSIS and WAIC over the experiments), written to the summary JSON as "loo_experiment"; with
 --sensitivity, the power-scaling sensitivity of every parameter column to the prior and to the likelihood (pyhillfit_amd/sensitivity.py),
-accumulated the same way and written to the summary JSON as "sensitivity".  The CMA-ES start point is replaced by a deterministic least-squares fit
+accumulated the same way and written to the summary JSON as "sensitivity"; with --next-dose G (single-level), the expected information
+gain of one further measurement at G candidate doses (pyhillfit_amd/design.py), accumulated the same way and written as "next_dose".  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -116,6 +118,25 @@ def check_args(parser, args):
             parser.error("--marginal-nodes must be one of %s" % ", ".join(str(q) for q in NODE_CHOICES))
         if args.marginal_every < 1:
             parser.error("--marginal-every must be >= 1")
+    if args.next_dose < 0:
+        parser.error("--next-dose must be >= 1 (0 = off)")
+    nd_given = [n for n in ("next_dose_concs", "next_dose_bins", "next_dose_every") if getattr(args, n, None) is not None]
+    if nd_given and not args.next_dose:
+        parser.error("--%s needs --next-dose" % nd_given[0].replace("_", "-"))
+    if args.next_dose and args.hierarchical:
+        parser.error("--next-dose is single-level only: the information of a new experiment under the population model of --hierarchical "
+                     "is a different integral")
+    if args.next_dose:
+        from . import design as ds
+        try:
+            if isinstance(args.next_dose_concs, str):
+                args.next_dose_concs = ds.parse_concs(args.next_dose_concs)
+            args.next_dose_bins = ds.check_bins(ds.DEFAULT_BINS if args.next_dose_bins is None else args.next_dose_bins)
+        except ValueError as e:
+            parser.error(str(e))
+        args.next_dose_every = ds.DEFAULT_EVERY if args.next_dose_every is None else args.next_dose_every
+        if args.next_dose_every < 1:
+            parser.error("--next-dose-every must be >= 1")
     de_given = [n for n in ("de_population", "de_gamma", "de_jump_every") if getattr(args, n, None) is not None]
     if args.de_every < 0:
         parser.error("--de-every must be >= 0 (0 = no differential-evolution moves)")
@@ -211,6 +232,17 @@ def build_parser():
                      "in [64, 4096] (default 4096)")
     new.add_argument("--sensitivity-threshold", type=float, default=None, metavar="TAU", help="--sensitivity: a column is flagged when its "
                      "sensitivity D exceeds TAU (default 0.05)")
+    new.add_argument("--next-dose", type=int, default=0, metavar="G", help="single-level: at which concentration should the next measurement be "
+                     "taken?  The expected information gain (nats) of ONE further measurement, recorded to 100/K %% block, at G doses "
+                     "log-spaced from the pair's smallest dose / 10 to its largest x 10 (and at the named --next-dose-concs), accumulated on "
+                     "the GPU while the rows stream past; a lower bound of the continuous value that rises with K; written to the summary "
+                     "JSON as \"next_dose\"")
+    new.add_argument("--next-dose-concs", type=str, default=None, metavar="C1,C2,...", help="--next-dose: further candidate doses in uM")
+    new.add_argument("--next-dose-bins", type=int, default=None, metavar="K", help="--next-dose: bins of (0, 100) the new response is recorded "
+                     "to, 128, 256 (default), 512 or 1024")
+    new.add_argument("--next-dose-every", type=int, default=None, metavar="T", help="--next-dose: every T-th post-burn-in row of every chain is "
+                     "used (default 17: on the whole Crumb set at the default chains, G = 16 and K = 256 the flag then adds no more than the "
+                     "sampling time; the cost is proportional to G K / T)")
     new.add_argument("--de-every", type=int, default=0, metavar="K", help="--hierarchical: differential-evolution moves between the chains of "
                      "each pair (ter Braak 2006) after every K iterations, K a multiple of the thinning (default 0 = off: every output as "
                      "without the flag); the chains of one population are then coupled; written to the summary JSON as \"de_moves\"")

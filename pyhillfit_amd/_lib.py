@@ -28,7 +28,8 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_replica_exchange_labels_init", "phf_replica_exchange_round", "phf_hier_de_workspace_bytes", "phf_hier_de_stats_bytes",
            "phf_hier_de_stats_init", "phf_hier_de_stats_read", "phf_hier_de_round", "phf_sensitivity_workspace_bytes", "phf_sensitivity_init",
            "phf_sensitivity_accumulate", "phf_sensitivity_reduce", "phf_sensitivity_components", "phf_batch_means_workspace_bytes",
-           "phf_batch_means_levels", "phf_batch_means_init", "phf_batch_means_accumulate", "phf_batch_means_reduce"]
+           "phf_batch_means_levels", "phf_batch_means_init", "phf_batch_means_accumulate", "phf_batch_means_reduce",
+           "phf_design_accumulator_doubles", "phf_design_rows_used", "phf_design_accumulate"]
 
 
 class PhfError(RuntimeError):
@@ -172,6 +173,10 @@ def load():
     lib.phf_batch_means_init.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp]
     lib.phf_batch_means_accumulate.argtypes = [vp, i64, i32, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
     lib.phf_batch_means_reduce.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
+    lib.phf_design_accumulator_doubles.argtypes = [i32]
+    lib.phf_design_rows_used.argtypes = [i64, i64, i32]
+    lib.phf_design_rows_used.restype = i64
+    lib.phf_design_accumulate.argtypes = [i32, i32, vp, i64, i32, i32, i32, i64, i32, vp, i32, i32, vp, C.c_size_t, vp]
     _lib = lib
     return lib
 

@@ -21,6 +21,7 @@ import torch
 
 from . import batch_means as bm
 from . import de_moves as de
+from . import design as ds
 from . import diagnostics as dg
 from . import loo as lo
 from . import marginal as mg
@@ -306,11 +307,31 @@ class SteppingStone(Analysis):
         self.acc.free()
 
 
+class Design(Analysis):
+    """--next-dose: the expected information gain of one further measurement at candidate doses (single-level only)"""
+    what, module = "--next-dose", ds
+    hint = "accumulators, {:.1f} GB are free: select fewer pairs, fewer candidate doses or a smaller --next-dose-bins"
+
+    def make(self, run):
+        a = run.args
+        doses = [ds.candidate_doses(c, a.next_dose, a.next_dose_concs) for c in run.concs]
+        self.check(ds.workspace_bytes(run.Q, len(doses[0]), a.next_dose_bins, run.C))
+        return ds.NextDose(run.kind, run.Q, run.C, doses, run.concs, a.next_dose_bins, a.next_dose_every, run.device)
+
+    def record(self, summ, q):
+        summ["next_dose"] = ds.json_record(self.res[q])
+
+    @classmethod
+    def report(cls, rank, names, group, args):
+        return [ds.report_line(rank, names, [r for a in group for r in a.per_problem()], args.next_dose)]
+
+
 def fit_analyses(args):
     """the analyses of a PyHillFit run, single-level or hierarchical, in the order they are built, fed, recorded and reported"""
     table = [(args.hierarchical and args.predictive_cdfs, PredictiveCdfs), (args.diagnostics, Diagnostics),
              (args.diagnostic_batch_means, BatchMeans), (args.de_every, DeMoves), (args.waic, Waic), (args.loo, Loo),
-             (args.leave_experiment_out, ExperimentLoo), (args.quantiles, Quantiles), (args.ppc, Ppc), (args.sensitivity, Sensitivity)]
+             (args.leave_experiment_out, ExperimentLoo), (args.quantiles, Quantiles), (args.ppc, Ppc), (args.sensitivity, Sensitivity),
+             (args.next_dose and not args.hierarchical, Design)]
     return [kind for on, kind in table if on]
 
 
