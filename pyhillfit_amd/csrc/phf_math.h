@@ -135,6 +135,37 @@ PHF_HD double phf_from_bits(uint64_t u) { double x; __builtin_memcpy(&x, &u, 8);
 PHF_HD double phf_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 PHF_HD double phf_sqrt(double x) { return __builtin_sqrt(x); } /* correctly rounded on both sides (checked in tests) */
 
+/* ------------------------------------------------------------------------------------------------ three-input bit forms (round 10)
+ * Two bit moves of the table-driven functions below as ONE v_bitop3_b32 each, where hipcc makes two or three instructions of the host's
+ * text ("round 10"; profiles/r10/).  Only the DEVICE path of a function calls them: the host path — what the twin in
+ * oracle/ compiles — keeps its text.  Both are bit identities with a plain-C body on the host, which compares them with the twin's
+ * expressions (tests/test_sl_intforms_host.py); no fp64 operation, branch or exec change is involved.  -DPHF_INT_...=0 keeps the
+ * parent's form of a part (same-source A/B builds: tools/build_exp_sl.sh). */
+#ifndef PHF_INT_REBIAS
+#define PHF_INT_REBIAS 1           /* (hi & 0xfffff) | 0x3ff00000, the mantissa under the exponent of 1.0 (phf_normal_u32, phf_log_ndtr_tab) */
+#endif
+#ifndef PHF_INT_SIGN
+#define PHF_INT_SIGN 1             /* phf_normal_u32: the sign bit of the word into |z| by one bit select */
+#endif
+
+/* (a & m) | o: truth table 0xEA */
+PHF_HD uint32_t phf_and_or_u32(uint32_t a, uint32_t m, uint32_t o) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_amdgcn_bitop3_b32((int)a, (int)m, (int)o, 0xEA);
+#else
+  return (a & m) | o;
+#endif
+}
+/* the bits of a where m has a one, the bits of b elsewhere: truth table 0xE4 */
+PHF_HD uint32_t phf_bit_select_u32(uint32_t a, uint32_t b, uint32_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_amdgcn_bitop3_b32((int)a, (int)b, (int)m, 0xE4);
+#else
+  return (a & m) | (b & ~m);
+#endif
+}
+PHF_HD double phf_from_words(uint32_t hi, uint32_t lo) { return phf_from_bits(((uint64_t)hi << 32) | lo); }
+
 /* Division and square root of the MH loops.  hipcc expands an fp64 division into v_div_scale x2, v_rcp_f64, two Newton steps,
  * q = n y, r = n - d q, v_div_fmas, v_div_fixup (11 instructions) and sqrt into a scaled v_rsq_f64 iteration (18): the scaling
  * and fix-up only serve operands within 2^+-~250 of the ends of the exponent range, zeros, infinities and NaNs.  The loops divide
@@ -830,7 +861,11 @@ PHF_HD double phf_log_ndtr_tab(double x, double y) {
   const uint64_t vb = phf_bits(y + 1.0);
   const uint32_t jr = (uint32_t)(vb >> 49) - (0x3ffu << 3);           /* 8 E + the top three mantissa bits */
   const uint32_t j = jr < (uint32_t)PHF_LOGPHI_TAB_N ? jr : (uint32_t)(PHF_LOGPHI_TAB_N - 1);
+#if defined(__HIP_DEVICE_COMPILE__) && PHF_INT_REBIAS
+  const double sft = phf_from_words(phf_and_or_u32((uint32_t)(vb >> 32), 0x000fffffu, 0x3ff00000u), (uint32_t)vb) - 1.0;
+#else
   const double sft = phf_from_bits((vb & 0x000fffffffffffffull) | 0x3ff0000000000000ull) - 1.0;
+#endif
   const phf_logphitab e = PHF_T_LOGPHI(j);
   double g = phf_fma(e.c[9], sft, e.c[8]);
   g = phf_fma(g, sft, e.c[7]);
@@ -992,7 +1027,36 @@ static __shared__ __attribute__((aligned(16))) phf_normtab phf_lds_normal[PHF_NO
 #define PHF_NORMAL_TABLE_TO_LDS() do { } while (0)
 #endif
 
+/* phf_normal_u32 as the device evaluates it (round 10): the same index, the same fp64 operations in the same order, the mantissa's
+ * re-bias and the sign transfer as one three-input operation each.  It compiles for the host too, where
+ * tests/test_sl_intforms_host.py compares it with phf_normal_u32 over all 2^32 words. */
+PHF_HD double phf_normal_u32_int(uint32_t v) {
+  const uint64_t ab = phf_bits((double)((v << 1) | 1u));
+  const uint32_t hi = (uint32_t)(ab >> 32);
+  const int j = (int)((hi - ((uint32_t)(0x3ff << 1) << 19)) >> 19);
+#if PHF_INT_REBIAS
+  const double sft = phf_from_words(phf_and_or_u32(hi, 0x000fffffu, 0x3ff00000u), (uint32_t)ab) - 1.0;
+#else
+  const double sft = phf_from_bits((ab & 0x000fffffffffffffull) | 0x3ff0000000000000ull) - 1.0;
+#endif
+  const phf_normtab e = PHF_T_NORMAL(j);
+  double z = phf_fma(e.c[5], sft, e.c[4]);
+  z = phf_fma(z, sft, e.c[3]);
+  z = phf_fma(z, sft, e.c[2]);
+  z = phf_fma(z, sft, e.c[1]);
+  z = phf_fma(z, sft, e.c[0]);
+#if PHF_INT_SIGN
+  const uint64_t zb = phf_bits(z);
+  return phf_from_words(phf_bit_select_u32((uint32_t)(zb >> 32), v, 0x7fffffffu), (uint32_t)zb);
+#else
+  return phf_from_bits((phf_bits(z) & 0x7fffffffffffffffull) | ((uint64_t)(v & 0x80000000u) << 32));
+#endif
+}
+
 PHF_HD double phf_normal_u32(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return phf_normal_u32_int(v);
+#else
   const uint64_t ab = phf_bits((double)((v << 1) | 1u));             /* a = 2 w + 1 in [1, 2^32): exact */
   const uint32_t hi = (uint32_t)(ab >> 32);
   /* 2 E + the top mantissa bit: 0..63; the bias leaves ahead of the shift (it has no bits below it), as in phf_log_pos_k */
@@ -1006,6 +1070,7 @@ PHF_HD double phf_normal_u32(uint32_t v) {
   z = phf_fma(z, sft, e.c[0]);
   /* |P| with the sign bit of v (one v_bfi_b32): exactly symmetric even where the polynomial's error crosses zero (p -> 1/2) */
   return phf_from_bits((phf_bits(z) & 0x7fffffffffffffffull) | ((uint64_t)(v & 0x80000000u) << 32));
+#endif
 }
 
 /* 53-bit uniform on [0,1) from two words — numpy's random_sample() construction

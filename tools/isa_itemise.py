@@ -5,6 +5,10 @@ kernel in a hipcc -S listing — what the vector-ALU slots of an iteration are s
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -S --cuda-device-only -o sl.s pyhillfit_amd/csrc/phf_single_level.hip
     python tools/isa_itemise.py sl.s mh_advance_kernelILi2ELb0ELi2E            (produced profiles/r05/c3_valu_itemised.txt)
 
+    python tools/isa_itemise.py sl.s mh_advance_kernelILi2ELb0ELi2E crumb [reference.s]
+                                                                               ("crumb": weight the bodies by the Crumb set's pairs; reference.s:
+                                                                               an earlier listing that names the bodies where the LDS reads cannot)
+
 A loop = a backward branch whose span holds no other backward branch; classes by opcode (and, for Philox, by its constants).  A region
 that a forward s_cbranch_vccz skips and that reads LDS (the accept test's logarithm) or holds six or more selects (the guarded Cholesky
 factor of the steady bodies) is a rare path and is listed apart, not counted."""
@@ -24,6 +28,7 @@ CLASSES = [
     ("moves (v_mov_b32 / _b64, v_accvgpr, lane ops)", r"v_(mov_b32|mov_b64|accvgpr_\w+|readlane\w*|writelane\w*|readfirstlane\w*|pk_mov_b32)"),
     ("integer / address arithmetic (table indices, exponent fields)", r"v_(and_b32|or_b32|not_b32|lshl\w*|lshr\w*|ashr\w*|add\w*_u32|add_co\w*|addc\w*|sub\w*_u32|subrev\w*|mul_u32_u24|mad_u32_u24|min_u32|max_u32|min_i32|max_i32|lshl_add_u64|bfe_\w+|cvt_\w*32\w*|cmp\w*_[ui]32|cmp\w*_[ui]64|alignbit\w*|perm_b32|add3_u32|lshl_or_b32|med3\w*)"),
 ]
+THREE_INPUT = "bit logic: three-input and-or / bit select (mantissa re-bias, sign transfer; not Philox)"
 
 
 # Issue cost in cycles per wavefront instruction with two or more wavefronts per SIMD, measured (tools/isa_instr_cost.py,
@@ -54,9 +59,88 @@ SHAPE_WEIGHTS = [((4, 1, 1), 45), ((4, 0, 0), 41), ((4, 2, 1), 25), ((4, 4, 1), 
                  ((2, 0, 0), 1), ((0, 4, 0), 3), ((0, 2, 0), 1), ((5, 0, 0), 2), ((5, 1, 0), 1)]
 
 
+def _vgprs(operand):
+    m = re.fullmatch(r"v(\d+)", operand)
+    if m:
+        return range(int(m.group(1)), int(m.group(1)) + 1)
+    m = re.fullmatch(r"v\[(\d+):(\d+)\]", operand)
+    return range(int(m.group(1)), int(m.group(2)) + 1) if m else range(0)
+
+
+def distinct_lds_bytes(body):
+    """how many different LDS bytes the ds_read instructions of a body fetch: per (address register, how often it has been written so far)
+    the union of the byte ranges read — a table word read again (a reload instead of a live register), or an entry fetched as
+    ds_read2_b64 pairs instead of 16-byte reads, counts once"""
+    version = collections.Counter()
+    seen = collections.defaultdict(set)
+    for l in body:
+        parts = l.replace(",", " ").split()
+        if l.startswith("ds_read"):
+            kind = parts[0][len("ds_read"):]
+            key = (parts[2], version[parts[2]])
+            if kind.startswith("2"):                                 # ds_read2[st64]_b32 / _b64: two elements at offset0, offset1 (in elements)
+                size = 8 if kind.endswith("b64") else 4
+                step = size * (64 if "st64" in kind else 1)
+                for name in ("offset0", "offset1"):
+                    m = re.search(name + r":(\d+)", l)
+                    start = (int(m.group(1)) if m else 0) * step
+                    seen[key].update(range(start, start + size))
+            else:
+                size = {"_b32": 4, "_b64": 8, "_b96": 12, "_b128": 16}[kind]
+                m = re.search(r"offset:(\d+)", l)
+                start = int(m.group(1)) if m else 0
+                seen[key].update(range(start, start + size))
+        if not re.match(r"(ds_write|global_store|buffer_store|scratch_store|s_|v_cmp)", l) and len(parts) > 1:
+            for r in _vgprs(parts[1]):
+                version["v%d" % r] += 1
+    return sum(len(v) for v in seen.values())
+
+
+def shape_by_lds(body):
+    nbytes = distinct_lds_bytes(body)
+    shared = int(any(l.startswith("ds_write") for l in body))
+    return next(((ko, kc, shared) for ko in range(0, 6) for kc in range(0, 5) if 200 + 8 * ko + 88 * kc == nbytes), None)
+
+
+def shape_key(body):
+    """what a body keeps from build to build: its fp64 fma / mul / add, estimates and ldexp (the twin fixes that sequence) and whether it
+    writes LDS slots"""
+    return tuple(sum(1 for l in body if re.match(p, l)) for p in (r"v_(fma|fmac|mul|add)_f64", r"v_(rcp|rsq)_f64", r"v_ldexp_f64")) + (
+        int(any(l.startswith("ds_write") for l in body)),)
+
+
+def reference_shapes(path, want):
+    """shape_key -> shape of the iteration bodies of an earlier listing whose LDS reads still name every shape (rounds 5 to 9): for
+    listings whose reads no longer do (fourth argument)"""
+    src = open(path).read().split("\n")
+    starts = [i for i, l in enumerate(src) if re.match(r"_Z\w+:", l)]
+    found = {}
+    for si, s0 in enumerate(starts):
+        if want not in src[s0].split(":", 1)[0]:
+            continue
+        labels, ins = {}, []
+        for l in src[s0 + 1:starts[si + 1] if si + 1 < len(starts) else len(src)]:
+            l = l.strip()
+            m = re.match(r"(\.LBB\d+_\d+):", l)
+            if m:
+                labels[m.group(1)] = len(ins)
+            elif l.startswith(".Lfunc_end"):
+                break
+            elif l and not l.startswith(";") and not l.startswith("."):
+                ins.append(l)
+        back = [(labels[m.group(1)], i) for i, l in enumerate(ins) for m in [re.match(r"s_cbranch_\w+ (\.LBB\d+_\d+)", l)]
+                if m and m.group(1) in labels and labels[m.group(1)] <= i]
+        for a, b in back:
+            if b - a > 300 and not any(a <= c and d <= b and (c, d) != (a, b) for c, d in back):
+                body = ins[a:b + 1]
+                found.setdefault(shape_key(body), set()).add(shape_by_lds(body))
+    return {k: next(iter(v)) for k, v in found.items() if len(v) == 1 and None not in v}
+
+
 def main():
     src = open(sys.argv[1]).read().split("\n")
     want = sys.argv[2]
+    reference = reference_shapes(sys.argv[4], want) if len(sys.argv) > 4 else {}
     starts = [i for i, l in enumerate(src) if re.match(r"_Z\w+:", l)]
     for si, s0 in enumerate(starts):
         name = src[s0].split(":", 1)[0]
@@ -110,6 +194,9 @@ def main():
                     c["(not VALU) " + ("s_nop" if op == "s_nop" else "scalar" if op.startswith("s_") else "LDS" if op.startswith("ds_") else
                                        "scratch" if op.startswith("scratch_") else "global memory" if op.startswith("global_") or op.startswith("buffer_") else op)] += 1
                     continue
+                if op.startswith("v_bitop3_b32") and "bitop3:0x96" not in l:
+                    c[THREE_INPUT] += 1                               # (Philox's is the three-input xor, table 0x96)
+                    continue
                 for cname, pat in CLASSES:
                     if re.fullmatch(pat + r"(_e32|_e64|_dpp|_sdwa)?", op):
                         c[cname] += 1
@@ -129,11 +216,14 @@ def main():
         # (one 2^(j/64) read per entry; five 16-byte reads of the log Phi table per censored entry; 13 for the draws and the logarithms;
         # a censored entry that shares its Hill denominator reads it from its LDS slot instead of the 2^(j/64) table), and LDS writes
         # (the uncensored entries' denominators to their slots) only in the shared-denominator bodies
+        # Counted in BYTES, each different byte once (distinct_lds_bytes): since round 10 the compiler reads some table words again where it
+        # used to keep them in registers, and fetches some entries as ds_read2_b64 pairs, so the number of read instructions no longer tells.
+        # 12 16-byte reads and one word for the draws and logarithms, one word per entry, 80 bytes of log Phi table per censored entry.
+        # Where even that fails (a table word read again through another address register), a reference listing given as fourth argument
+        # names the body: the one of its bodies with the same fp64 arithmetic count and the same use of the LDS slots.
         shapes = {}
         for valu, fp, a, b, c in rows:
-            reads = sum(1 for l in ins[a:b + 1] if l.startswith("ds_read"))
-            shared = int(any(l.startswith("ds_write") for l in ins[a:b + 1]))
-            shapes[a] = next(((ko, kc, shared) for ko in range(0, 6) for kc in range(0, 5) if 13 + ko + 6 * kc == reads), None)
+            shapes[a] = reference.get(shape_key(ins[a:b + 1])) if reference else shape_by_lds(ins[a:b + 1])
         weights = {}
         if len(sys.argv) > 3 and sys.argv[3] == "crumb":
             have = set(shapes.values())
