@@ -420,6 +420,31 @@ int phf_batch_means_accumulate(const double* rows, int64_t num_rows, int num_pro
 int phf_batch_means_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, const double* workspace,
                            size_t workspace_bytes, double* out, void* stream);
 
+/* ---- posterior correlations and multivariate R-hat: co-moments of the parameter columns per half-chain -------------------------
+ * The one analysis that looks ACROSS columns.  Half-chains as for phf_diagnostics_* (h = floor(total_rows / 2) >= 4, M = 2C, the
+ * middle row of an odd total_rows is never read).  Per (problem, half, chain), with y = x - (the half's first row) over the
+ * d = num_columns columns 0..d-1 of a row: S_i = sum y_i and P_ij = sum y_i y_j (i <= j), as S <- S + y and P <- fma(y_i, y_j, P)
+ * in row order, a row count, and a flag set by a row with a non-finite y (such a half-chain is dropped whole by the reduction).
+ * Deterministic: no atomics, bit-identical however the rows are cut into accumulate calls (pyhillfit_amd/csrc/phf_comoments.h
+ * holds the rules, the workspace layout and the reduction order; its host build is the kernels' twin).  rows, first_row,
+ * total_rows, stream: as for phf_diagnostics_accumulate; the same error codes.  num_columns <= 1024.
+ *   workspace  device, phf_comoments_workspace_bytes(...) = num_problems * 2 * num_chains * (2d + d(d+1)/2 + 2) doubles, laid out
+ *              [problem][half][field][chain] with the fields x0[d] | S[d] | P[d(d+1)/2] (row-major upper triangle) | rows | flag;
+ *              phf_comoments_init zeroes it (stream-ordered)
+ *   out        device [num_problems][2 d(d+1)/2 + 2d + 4]: W (the mean over the m used half-chains of their sample covariances,
+ *              divisor h - 1), B/h (the sample covariance of their means, divisor m - 1; both as upper triangles), the grand mean
+ *              [d], the sum over half-chains of (mean - the first used half-chain's mean) [d], m, the number of half-chains dropped,
+ *              h, and a spare 0; valid once all total_rows rows have arrived.  W is 0 when m = 0 and B/h when m < 2.
+ * phf_comoments_workspace_bytes returns 0 for an invalid shape (phf_last_error() says why). */
+size_t phf_comoments_workspace_bytes(int num_problems, int num_columns, int num_chains, int64_t total_rows);
+int phf_comoments_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, double* workspace, size_t workspace_bytes,
+                       void* stream);
+int phf_comoments_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
+                             int num_columns, int64_t first_row, int64_t total_rows, double* workspace, size_t workspace_bytes,
+                             void* stream);
+int phf_comoments_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, const double* workspace,
+                         size_t workspace_bytes, double* out, void* stream);
+
 /* ---- pointwise log-likelihood and WAIC -------------------------------------------------------------------------------------
  * The terms are per DATA POINT (not per merged entry).  Points of problem q are row q of the arrays, in any order the caller keeps
  * (pyhillfit_amd/waic.py: data-file order); point p < count[q] of problem q has log-likelihood, for one parameter vector:

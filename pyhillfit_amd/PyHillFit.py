@@ -9,7 +9,7 @@
            [--hierarchical --leave-experiment-out [--marginal-nodes 128] [--marginal-every T]]
            [--sensitivity [--sensitivity-delta 0.01] [--sensitivity-bins 4096] [--sensitivity-threshold 0.05]]
            [--hierarchical --de-every K [--de-population 64] [--de-gamma GAMMA] [--de-jump-every 10]]
-           [--next-dose G [--next-dose-concs c1,c2,...] [--next-dose-bins 256] [--next-dose-every 17]]
+           [--next-dose G [--next-dose-concs c1,c2,...] [--next-dose-bins 256] [--next-dose-every 17]] [--correlations]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -29,7 +29,9 @@ predicted future experiment at G doses (and at the named --band-concs), accumula
 (Hill_i, pIC50_i) integrated out on the GPU, PSIS and WAIC over the experiments), written to the summary JSON as "loo_experiment"; with
 --sensitivity, the power-scaling sensitivity of every parameter column to the prior and to the likelihood (pyhillfit_amd/sensitivity.py),
 accumulated the same way and written to the summary JSON as "sensitivity"; with --next-dose G (single-level), the expected information
-gain of one further measurement at G candidate doses (pyhillfit_amd/design.py), accumulated the same way and written as "next_dose".  The CMA-ES start point is replaced by a deterministic least-squares fit
+gain of one further measurement at G candidate doses (pyhillfit_amd/design.py), accumulated the same way and written as "next_dose"; with --correlations, the posterior and within-chain correlation matrices of the
+parameter columns and the multivariate R-hat with the direction along which the chains sit apart (pyhillfit_amd/correlations.py),
+accumulated the same way and written as "correlations".  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -243,6 +245,11 @@ def build_parser():
     new.add_argument("--next-dose-every", type=int, default=None, metavar="T", help="--next-dose: every T-th post-burn-in row of every chain is "
                      "used (default 17: on the whole Crumb set at the default chains, G = 16 and K = 256 the flag then adds no more than the "
                      "sampling time; the cost is proportional to G K / T)")
+    new.add_argument("--correlations", action='store_true', default=False, help="the posterior correlation matrix of the parameter columns "
+                     "over all chains, the within-chain correlation matrix and its principal axes, and the multivariate R-hat (Brooks & Gelman "
+                     "1998, in the convention of the split-R-hat) with the linear combination of the parameters along which the chains "
+                     "disagree most, from co-moments accumulated on the GPU while the rows stream past; written to the summary JSON as "
+                     "\"correlations\"")
     new.add_argument("--de-every", type=int, default=0, metavar="K", help="--hierarchical: differential-evolution moves between the chains of "
                      "each pair (ter Braak 2006) after every K iterations, K a multiple of the thinning (default 0 = off: every output as "
                      "without the flag); the chains of one population are then coupled; written to the summary JSON as \"de_moves\"")

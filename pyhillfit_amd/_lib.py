@@ -29,7 +29,8 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_hier_de_stats_init", "phf_hier_de_stats_read", "phf_hier_de_round", "phf_sensitivity_workspace_bytes", "phf_sensitivity_init",
            "phf_sensitivity_accumulate", "phf_sensitivity_reduce", "phf_sensitivity_components", "phf_batch_means_workspace_bytes",
            "phf_batch_means_levels", "phf_batch_means_init", "phf_batch_means_accumulate", "phf_batch_means_reduce",
-           "phf_design_accumulator_doubles", "phf_design_rows_used", "phf_design_accumulate"]
+           "phf_design_accumulator_doubles", "phf_design_rows_used", "phf_design_accumulate", "phf_comoments_workspace_bytes",
+           "phf_comoments_init", "phf_comoments_accumulate", "phf_comoments_reduce"]
 
 
 class PhfError(RuntimeError):
@@ -177,6 +178,11 @@ def load():
     lib.phf_design_rows_used.argtypes = [i64, i64, i32]
     lib.phf_design_rows_used.restype = i64
     lib.phf_design_accumulate.argtypes = [i32, i32, vp, i64, i32, i32, i32, i64, i32, vp, i32, i32, vp, C.c_size_t, vp]
+    lib.phf_comoments_workspace_bytes.argtypes = [i32, i32, i32, i64]
+    lib.phf_comoments_workspace_bytes.restype = C.c_size_t
+    lib.phf_comoments_init.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp]
+    lib.phf_comoments_accumulate.argtypes = [vp, i64, i32, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
+    lib.phf_comoments_reduce.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
     _lib = lib
     return lib
 

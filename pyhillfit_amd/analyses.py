@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import batch_means as bm
+from . import correlations as cr
 from . import de_moves as de
 from . import design as ds
 from . import diagnostics as dg
@@ -326,12 +327,29 @@ class Design(Analysis):
         return [ds.report_line(rank, names, [r for a in group for r in a.per_problem()], args.next_dose)]
 
 
+class Correlations(Analysis):
+    """--correlations: the posterior and within-chain correlation matrices of the parameter columns (the log-target is left out, as
+    --sensitivity leaves it out) and the multivariate R-hat"""
+    what, module, hint = "--correlations", cr, "co-moments, {:.1f} GB are free: select fewer pairs or fewer chains"
+
+    def make(self, run):
+        self.check(cr.workspace_bytes(run.Q, run.cols - 1, run.C, run.rows))
+        return cr.PosteriorCorrelations(run.Q, run.C, run.columns[:-1], run.rows, run.device)
+
+    def record(self, summ, q):
+        run = self.run
+        summ["correlations"] = cr.json_record(self.res[q])
+        if run.de is not None:                                            # B is then taken over dependent chains
+            summ["correlations"]["chains_coupled_within_populations_of"] = run.de.G
+            summ["correlations"]["note"] = de.COUPLING_NOTE.format(G=run.de.G)
+
+
 def fit_analyses(args):
     """the analyses of a PyHillFit run, single-level or hierarchical, in the order they are built, fed, recorded and reported"""
     table = [(args.hierarchical and args.predictive_cdfs, PredictiveCdfs), (args.diagnostics, Diagnostics),
              (args.diagnostic_batch_means, BatchMeans), (args.de_every, DeMoves), (args.waic, Waic), (args.loo, Loo),
              (args.leave_experiment_out, ExperimentLoo), (args.quantiles, Quantiles), (args.ppc, Ppc), (args.sensitivity, Sensitivity),
-             (args.next_dose and not args.hierarchical, Design)]
+             (args.next_dose and not args.hierarchical, Design), (args.correlations, Correlations)]
     return [kind for on, kind in table if on]
 
 

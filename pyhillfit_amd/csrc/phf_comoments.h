@@ -1,0 +1,225 @@
+/* phf_comoments.h — co-moments of the parameter columns, per half-chain, accumulated while the rows stream past: what the posterior
+ * correlation matrix, the within- and between-chain covariance matrices W and B/h and the multivariate R-hat are made of
+ * (pyhillfit_amd/correlations.py; DESIGN.md §3, "Posterior correlations").  The scalar rules here are shared by the gfx950 kernels
+ * (phf_comoments.hip) and a host build (tests/test_correlations_host.py), like phf_batch_means.h.  Plain C, compiled with
+ * -ffp-contract=off: every fma is spelled, everything else is a single rounded operation in the order written here.
+ *
+ * A chain of N rows gives two half-chains of h = floor(N/2) rows, as in phf_diagnostics.hip: half 0 = rows 0..h-1, half 1 = the last h
+ * rows (the middle row of an odd N is dropped, never read).  Within a half, row m carries y_i = x_i - x0_i for the d parameter columns
+ * (x0 the half's first row: a pIC50 of 4.548 +- 0.002 keeps its digits).  Per (problem, half, chain):
+ *     S_i  <- S_i + y_i                 (i = 0..d-1)
+ *     P_ij <- fma(y_i, y_j, P_ij)       (i <= j)
+ * in row order, a row count, and a flag that is set once a row holds a y that is not finite (the half-chain is then dropped whole by
+ * the reduction; its accumulators are not used).  Every accumulator is its own sequential chain of operations and round-trips
+ * through memory exactly, so the state is bit-identical however the rows are cut into calls and however the pairs are tiled.
+ *
+ * State: PHF_CM_FIELDS(d) doubles per (problem, half, chain), field f of chain c at ws[((q * 2 + half) * F + f) * C + c] (the chain
+ * index is fastest in memory):  x0[d] | S[d] | P[d (d + 1) / 2] (row-major upper triangle) | rows | flag.
+ *
+ * Reduction over the M = 2C half-chains, k = 2 c + half: lane l of 64 takes chains l, l + 64, .. (half 0 then half 1), skips the
+ * flagged ones, and the 64 partial sums are added by a butterfly over lane distances 32, 16, .., 1 (phf_cm_lane_* below; the host
+ * build runs the same functions and the same butterfly).  With m the half-chains used:
+ *     cov_k,ij = (P_ij - S_i S_j / h) / (h - 1),   W_ij = (sum_k cov_k,ij) / m,
+ *     z_k,i = (x0_i + S_i / h) - ref_i  with ref the mean of the FIRST USED half-chain (half-chain 0 unless it was dropped),
+ *     T_i = sum_k z_k,i,   U_ij = sum_k fma(z_k,i, z_k,j, .),   (B/h)_ij = (U_ij - T_i T_j / m) / (m - 1),   mean_i = ref_i + T_i / m.
+ * Output per problem, PHF_CM_OUT_DOUBLES(d):  W[np] | B/h[np] | mean[d] | T[d] | m | dropped | h | 0.   W is 0 when m = 0, B/h when m < 2. */
+#ifndef PHF_COMOMENTS_H
+#define PHF_COMOMENTS_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifndef PHF_HD
+#if defined(__HIPCC__)
+#define PHF_HD static __host__ __device__ __forceinline__
+#else
+#define PHF_HD static inline __attribute__((always_inline))
+#endif
+#endif
+
+#define PHF_CM_LANES 64
+#define PHF_CM_MIN_HALF 4                                         /* h >= 4, as phf_diagnostics requires */
+#define PHF_CM_PAIRS(d) ((d) * ((d) + 1) / 2)
+#define PHF_CM_FIELDS(d) (2 * (d) + PHF_CM_PAIRS(d) + 2)
+#define PHF_CM_OUT_DOUBLES(d) (2 * PHF_CM_PAIRS(d) + 2 * (d) + 4)
+
+/* index of (i, j), i <= j, in the row-major upper triangle of a d x d matrix */
+PHF_HD int phf_cm_pair(int d, int i, int j) { return i * d - i * (i - 1) / 2 + (j - i); }
+
+PHF_HD int phf_cm_x0(int i) { return i; }
+PHF_HD int phf_cm_s(int d, int i) { return d + i; }
+PHF_HD int phf_cm_p(int d, int p) { return 2 * d + p; }
+PHF_HD int phf_cm_rows(int d) { return 2 * d + PHF_CM_PAIRS(d); }
+PHF_HD int phf_cm_flag(int d) { return 2 * d + PHF_CM_PAIRS(d) + 1; }
+
+/* which half row n of N belongs to, and its index m there; -1: the dropped middle row of an odd N */
+PHF_HD int phf_cm_half_of(int64_t total_rows, int64_t n, int64_t* m) {
+  const int64_t h = total_rows / 2;
+  if (n < h) { *m = n; return 0; }
+  if (n >= total_rows - h) { *m = n - (total_rows - h); return 1; }
+  *m = 0;
+  return -1;
+}
+
+PHF_HD int phf_cm_finite(double v) { return (v - v) == 0.0; }
+
+/* the two accumulation steps */
+PHF_HD double phf_cm_add(double s, double y) { return s + y; }
+PHF_HD double phf_cm_mad(double p, double yi, double yj) { return __builtin_fma(yi, yj, p); }
+
+/* a closed half-chain: its sample covariance (divisor h - 1) and its mean */
+PHF_HD double phf_cm_cov(double p, double si, double sj, double h) {
+  const double t = si * sj;
+  const double u = t / h;
+  return (p - u) / (h - 1.0);
+}
+PHF_HD double phf_cm_mean(double x0, double s, double h) { return x0 + s / h; }
+
+/* the state of half-chain (c, half) of one problem: st[f * C] is field f */
+PHF_HD const double* phf_cm_state(const double* wsq, size_t C, int d, int c, int half) {
+  return wsq + (size_t)half * PHF_CM_FIELDS(d) * C + (size_t)c;
+}
+
+/* lane's count of the used half-chains and the least k = 2 c + half among them (2 C when it has none) */
+PHF_HD void phf_cm_lane_used(const double* wsq, int C, int d, int lane, int* used, int* first) {
+  int n = 0, k0 = 2 * C;
+  for (int c = lane; c < C; c += PHF_CM_LANES)
+    for (int half = 0; half < 2; ++half)
+      if (phf_cm_state(wsq, (size_t)C, d, c, half)[(size_t)phf_cm_flag(d) * C] == 0.0) {
+        if (n == 0) k0 = 2 * c + half;
+        ++n;
+      }
+  *used = n;
+  *first = k0;
+}
+
+/* mean of column i of half-chain k = 2 c + half */
+PHF_HD double phf_cm_mean_of(const double* wsq, int C, int d, double h, int k, int i) {
+  const double* st = phf_cm_state(wsq, (size_t)C, d, k >> 1, k & 1);
+  return phf_cm_mean(st[(size_t)phf_cm_x0(i) * C], st[(size_t)phf_cm_s(d, i) * C], h);
+}
+
+/* lane's partial sums of pair (i, j): sums[0] = sum cov, [1] = sum z_i, [2] = sum z_j, [3] = sum z_i z_j */
+PHF_HD void phf_cm_lane_pair(const double* wsq, int C, int d, double h, int i, int j, double refi, double refj, int lane, double* sums) {
+  double sc = 0.0, ti = 0.0, tj = 0.0, u = 0.0;
+  const int p = phf_cm_pair(d, i, j);
+  for (int c = lane; c < C; c += PHF_CM_LANES)
+    for (int half = 0; half < 2; ++half) {
+      const double* st = phf_cm_state(wsq, (size_t)C, d, c, half);
+      if (st[(size_t)phf_cm_flag(d) * C] != 0.0) continue;
+      const double si = st[(size_t)phf_cm_s(d, i) * C], sj = st[(size_t)phf_cm_s(d, j) * C];
+      sc = sc + phf_cm_cov(st[(size_t)phf_cm_p(d, p) * C], si, sj, h);
+      const double zi = phf_cm_mean(st[(size_t)phf_cm_x0(i) * C], si, h) - refi;
+      const double zj = phf_cm_mean(st[(size_t)phf_cm_x0(j) * C], sj, h) - refj;
+      ti = ti + zi;
+      tj = tj + zj;
+      u = __builtin_fma(zi, zj, u);
+    }
+  sums[0] = sc; sums[1] = ti; sums[2] = tj; sums[3] = u;
+}
+
+/* lane's partial sum of z_i alone: the same terms in the same order as sums[1] above */
+PHF_HD double phf_cm_lane_mean(const double* wsq, int C, int d, double h, int i, double refi, int lane) {
+  double ti = 0.0;
+  for (int c = lane; c < C; c += PHF_CM_LANES)
+    for (int half = 0; half < 2; ++half) {
+      const double* st = phf_cm_state(wsq, (size_t)C, d, c, half);
+      if (st[(size_t)phf_cm_flag(d) * C] != 0.0) continue;
+      ti = ti + (phf_cm_mean(st[(size_t)phf_cm_x0(i) * C], st[(size_t)phf_cm_s(d, i) * C], h) - refi);
+    }
+  return ti;
+}
+
+/* from the sums over all lanes: W_ij and (B/h)_ij */
+PHF_HD void phf_cm_finish_pair(const double* sums, int m, double* w, double* bh) {
+  const double md = (double)m;
+  *w = m >= 1 ? sums[0] / md : 0.0;
+  *bh = m >= 2 ? (sums[3] - sums[1] * sums[2] / md) / (md - 1.0) : 0.0;
+}
+PHF_HD double phf_cm_finish_mean(double ref, double t, int m) { return m >= 1 ? ref + t / (double)m : 0.0; }
+
+#if !defined(__HIPCC__)
+/* ---- the host build: the same operations in the same order as the kernels --------------------------------------------------- */
+
+/* rows [num_rows][Q][stride][C], the rows first_row .. of total_rows; ws [Q][2][F][C], zeroed before the first call */
+static void phf_cm_accumulate_host(const double* rows, int64_t num_rows, int Q, int stride, int C, int d, int64_t first_row,
+                                   int64_t total_rows, double* ws) {
+  const size_t F = (size_t)PHF_CM_FIELDS(d), Cs = (size_t)C, rstep = (size_t)Q * stride * Cs;
+  for (int q = 0; q < Q; ++q)
+    for (int c = 0; c < C; ++c)
+      for (int64_t r = 0; r < num_rows; ++r) {
+        int64_t m;
+        const int half = phf_cm_half_of(total_rows, first_row + r, &m);
+        if (half < 0) continue;
+        const double* x = rows + (size_t)r * rstep + (size_t)q * stride * Cs + c;
+        double* st = ws + ((size_t)q * 2 + half) * F * Cs + c;
+        int bad = 0;
+        if (m == 0)
+          for (int i = 0; i < d; ++i) st[(size_t)phf_cm_x0(i) * Cs] = x[(size_t)i * Cs];
+        for (int i = 0; i < d; ++i) {
+          const double yi = x[(size_t)i * Cs] - st[(size_t)phf_cm_x0(i) * Cs];
+          if (!phf_cm_finite(yi)) bad = 1;
+          st[(size_t)phf_cm_s(d, i) * Cs] = phf_cm_add(st[(size_t)phf_cm_s(d, i) * Cs], yi);
+          for (int j = i; j < d; ++j) {
+            const double yj = x[(size_t)j * Cs] - st[(size_t)phf_cm_x0(j) * Cs];
+            double* p = st + (size_t)phf_cm_p(d, phf_cm_pair(d, i, j)) * Cs;
+            *p = phf_cm_mad(*p, yi, yj);
+          }
+        }
+        st[(size_t)phf_cm_rows(d) * Cs] = (double)(m + 1);
+        if (bad) st[(size_t)phf_cm_flag(d) * Cs] = 1.0;
+      }
+}
+
+/* v[0] of the butterfly every lane of a wavefront runs: v[l] <- v[l] + v[l ^ o] for o = 32, 16, .., 1 */
+static double phf_cm_butterfly_host(double* v) {
+  double t[PHF_CM_LANES];
+  for (int o = PHF_CM_LANES / 2; o > 0; o >>= 1) {
+    for (int l = 0; l < PHF_CM_LANES; ++l) t[l] = v[l] + v[l ^ o];
+    for (int l = 0; l < PHF_CM_LANES; ++l) v[l] = t[l];
+  }
+  return v[0];
+}
+
+/* ws [Q][2][F][C] with all total_rows rows accumulated -> out [Q][PHF_CM_OUT_DOUBLES(d)] */
+static void phf_cm_reduce_host(const double* ws, int Q, int C, int d, int64_t total_rows, double* out) {
+  const int np = PHF_CM_PAIRS(d);
+  const double h = (double)(total_rows / 2);
+  for (int q = 0; q < Q; ++q) {
+    const double* wsq = ws + (size_t)q * 2 * PHF_CM_FIELDS(d) * C;
+    double* o = out + (size_t)q * PHF_CM_OUT_DOUBLES(d);
+    int m = 0, first = 2 * C;
+    for (int lane = 0; lane < PHF_CM_LANES; ++lane) {
+      int n, k0;
+      phf_cm_lane_used(wsq, C, d, lane, &n, &k0);
+      m += n;
+      if (k0 < first) first = k0;
+    }
+    for (int i = 0; i < d; ++i) {
+      const double refi = m >= 1 ? phf_cm_mean_of(wsq, C, d, h, first, i) : 0.0;
+      double v[PHF_CM_LANES];
+      for (int lane = 0; lane < PHF_CM_LANES; ++lane) v[lane] = phf_cm_lane_mean(wsq, C, d, h, i, refi, lane);
+      const double t = phf_cm_butterfly_host(v);
+      o[2 * np + i] = phf_cm_finish_mean(refi, t, m);
+      o[2 * np + d + i] = t;
+      for (int j = i; j < d; ++j) {
+        const double refj = m >= 1 ? phf_cm_mean_of(wsq, C, d, h, first, j) : 0.0;
+        double part[4][PHF_CM_LANES], sums[4];
+        for (int lane = 0; lane < PHF_CM_LANES; ++lane) {
+          double s[4];
+          phf_cm_lane_pair(wsq, C, d, h, i, j, refi, refj, lane, s);
+          for (int k = 0; k < 4; ++k) part[k][lane] = s[k];
+        }
+        for (int k = 0; k < 4; ++k) sums[k] = phf_cm_butterfly_host(part[k]);
+        phf_cm_finish_pair(sums, m, &o[phf_cm_pair(d, i, j)], &o[np + phf_cm_pair(d, i, j)]);
+      }
+    }
+    o[2 * np + 2 * d] = (double)m;
+    o[2 * np + 2 * d + 1] = (double)(2 * C - m);
+    o[2 * np + 2 * d + 2] = h;
+    o[2 * np + 2 * d + 3] = 0.0;
+  }
+}
+#endif /* !__HIPCC__ */
+
+#endif /* PHF_COMOMENTS_H */
