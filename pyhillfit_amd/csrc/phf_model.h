@@ -252,7 +252,11 @@ PHF_HD void phf_sl_log_target_shared(int model, const double* lc, const double* 
  * pic50 >= PHF_PIC50_LOWER, so ln_ic50 <= 9 ln 10 = 20.8 and the argument a = hill (ln_conc - ln_ic50) >= 10 (-50 - 20.8) = -708 (model 1:
  * >= -70.8), far above -746 (fmax(a, -746) = a: the same double).  Outside the support the exponential may return anything — the
  * proposal is rejected by the predicate — and its table index is masked (phf_exp_core_k: n & 63), so no address depends on it.  A NaN
- * argument is still dropped by the upper cap fmin(a, PHF_HILL_ARG_CAP), which stays. */
+ * argument is still dropped by the upper cap fmin(a, PHF_HILL_ARG_CAP), which stays.
+ * temp0_select == 0 promises that the temperature is neither +-0 nor NaN: the select lik = 0 at temperature 0 (two v_cndmask_b32 on a
+ * wave-uniform condition, every iteration) then never fires and is left out; the multiply stays (round 11).
+ * A shared censored entry m reads the double at BYTE offset den_byte_off[m] from den_read: the samplers pass offsets computed once per call
+ * from the base of all lanes' slots; den_byte_off[m] = 8 den_off[m] with den_read = den_slot is the form above. */
 #define PHF_LN_CONC_NOCLAMP (-50.0)
 #if defined(__cplusplus)
 static_assert(PHF_SIGMA_FLOOR == PHF_SIGMA_LOC, "sigma <= floor must imply outside");
@@ -265,12 +269,13 @@ PHF_HD double phf_hill_den_sampler(int model, double ln_conc, double hill, doubl
   return 1.0 + (lower_clamp ? phf_exp_capped_k(c, k_exp) : phf_exp_core_k(c, k_exp));
 }
 #define PHF_DEN_(jj) phf_hill_den_sampler(model, lc[jj], hill, ln_ic50, lower_clamp, k_exp)
-#define PHF_CDEN_S_(jj) ((((share_mask) >> ((jj) - n_other)) & 1u) ? den_slot[den_off[(jj) - n_other]] : PHF_DEN_(jj))
-PHF_HD int phf_sl_log_target_sampler(int model, const double* lc, const double* y, const double* w, int n_other, int n_cens,
-                                     double n_other_points, double ss_within, double pi_bit, double temperature, int lower_clamp,
-                                     const double* th, phf_ktab k_exp, phf_ktab k_log,
-                                     unsigned share_mask, const int* den_off, double* den_slot, int slot_stride,
-                                     double* out_lik, double* out_prior, double* out_ll1, double* out_lt) {
+#define PHF_CDEN_S_(jj) ((((share_mask) >> ((jj) - n_other)) & 1u) ? *(const double*)((const char*)den_read + den_byte_off[(jj) - n_other]) \
+                                                                   : PHF_DEN_(jj))
+PHF_HD int phf_sl_log_target_sampler_t(int model, const double* lc, const double* y, const double* w, int n_other, int n_cens,
+                                       double n_other_points, double ss_within, double pi_bit, double temperature, int lower_clamp,
+                                       int temp0_select, const double* th, phf_ktab k_exp, phf_ktab k_log,
+                                       unsigned share_mask, const int* den_byte_off, const double* den_read, double* den_slot, int slot_stride,
+                                       double* out_lik, double* out_prior, double* out_ll1, double* out_lt) {
   const double pic50 = th[0];
   const double hill = (model == 1) ? 1.0 : th[1];
   const double sigma = (model == 1) ? th[1] : th[2];
@@ -344,10 +349,23 @@ PHF_HD int phf_sl_log_target_sampler(int model, const double* lc, const double* 
   const double lp = -PHF_PIC50_RATE * pic50 + g;
   *out_prior = lp;
   double lik = temperature * a;
-  if (temperature == 0.0) lik = 0.0;
+  if (temp0_select && temperature == 0.0) lik = 0.0;
   *out_lik = lik;
   *out_lt = lik + lp;
   return outside;
+}
+/* For every temperature (the select stays), with the arguments of before round 11: what the host tests call.  It is now a wrapper, so those
+ * tests run the body above through the byte-offset form of the shared read, (const char*) den_read + 8 den_off[m]: the same address as
+ * den_slot[den_off[m]].  One offset per bit of share_mask (32), of which an entry is read only where its bit is set. */
+PHF_HD int phf_sl_log_target_sampler(int model, const double* lc, const double* y, const double* w, int n_other, int n_cens,
+                                     double n_other_points, double ss_within, double pi_bit, double temperature, int lower_clamp,
+                                     const double* th, phf_ktab k_exp, phf_ktab k_log,
+                                     unsigned share_mask, const int* den_off, double* den_slot, int slot_stride,
+                                     double* out_lik, double* out_prior, double* out_ll1, double* out_lt) {
+  int byte_off[32];
+  for (int m = 0; m < n_cens && m < 32; ++m) byte_off[m] = ((share_mask >> m) & 1u) ? 8 * den_off[m] : 0;
+  return phf_sl_log_target_sampler_t(model, lc, y, w, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature, lower_clamp, 1, th,
+                                     k_exp, k_log, share_mask, byte_off, den_slot, den_slot, slot_stride, out_lik, out_prior, out_ll1, out_lt);
 }
 #undef PHF_DEN_
 #undef PHF_CDEN_S_
@@ -377,9 +395,7 @@ PHF_HD double phf_sl_log_prior(int model, const double* th, phf_ktab k_log) {
  * Stateless: a function of (chain, problem, t, seed) alone, so a launch, a quantum or the twin may start anywhere.
  * Returns log(u) (PyHillFit.py:834-835) and the d standard normals in z (PyHillFit.py:831); z[2] = 0 for d == 2.
  * (Rounds 1-3 drew the normals by Box-Muller from 24- / 32-bit fields; the inverse CDF costs a third of the fp64 operations.) */
-PHF_HD double phf_mh_draws(int d, uint32_t chain_id, uint32_t problem_id, uint32_t t, uint32_t seed_lo,
-                           uint32_t seed_hi, phf_ktab k_log, double* z) {
-  const phf_u32x4 b = phf_philox_mh(chain_id, problem_id, t, 0u, seed_lo, seed_hi);
+PHF_HD double phf_mh_draws_of_block(int d, phf_u32x4 b, phf_ktab k_log, double* z) {
   z[0] = phf_normal_u32(b.w[0]);
   z[1] = phf_normal_u32(b.w[1]);
   if (d == 2) {
@@ -391,15 +407,36 @@ PHF_HD double phf_mh_draws(int d, uint32_t chain_id, uint32_t problem_id, uint32
   z[2] = phf_normal_u32(b.w[2]);
   return phf_log_pos_k(phf_unit_open32(b.w[3]), k_log);  /* u = (w + 1/2) / 2^32 is never 0 */
 }
+PHF_HD double phf_mh_draws(int d, uint32_t chain_id, uint32_t problem_id, uint32_t t, uint32_t seed_lo,
+                           uint32_t seed_hi, phf_ktab k_log, double* z) {
+  const phf_u32x4 b = phf_philox_mh(chain_id, problem_id, t, 0u, seed_lo, seed_hi);
+  return phf_mh_draws_of_block(d, b, k_log, z);
+}
 
 /* d == 3 only: the same block and the same three normals as phf_mh_draws, and the accept WORD w (u = (w + 1/2) / 2^32) in place of
  * log u — for phf_mh_accept_u32, which decides log u < x without the logarithm for nearly every w. */
-PHF_HD uint32_t phf_mh_draws_w3(uint32_t chain_id, uint32_t problem_id, uint32_t t, uint32_t seed_lo, uint32_t seed_hi, double* z) {
-  const phf_u32x4 b = phf_philox_mh(chain_id, problem_id, t, 0u, seed_lo, seed_hi);
+PHF_HD uint32_t phf_mh_draws_w3_of_block(phf_u32x4 b, double* z) {
   z[0] = phf_normal_u32(b.w[0]);
   z[1] = phf_normal_u32(b.w[1]);
   z[2] = phf_normal_u32(b.w[2]);
   return b.w[3];
+}
+PHF_HD uint32_t phf_mh_draws_w3(uint32_t chain_id, uint32_t problem_id, uint32_t t, uint32_t seed_lo, uint32_t seed_hi, double* z) {
+  const phf_u32x4 b = phf_philox_mh(chain_id, problem_id, t, 0u, seed_lo, seed_hi);
+  return phf_mh_draws_w3_of_block(b, z);
+}
+
+/* phf_mh_draws / phf_mh_draws_w3 for the samplers' two-wavefront build: the same block from phf_philox_mh_t_uniform (phf_philox.h: seed_lo_u
+ * and seed_hi_w1_u are wave-uniform copies of seed_lo and of seed_hi + 0xBB67AE85), the same conversions.  Device path only. */
+PHF_HD double phf_mh_draws_uniform(int d, uint32_t chain_id, uint32_t problem_id, uint32_t t, uint32_t seed_lo, uint32_t seed_hi,
+                                   uint32_t seed_lo_u, uint32_t seed_hi_w1_u, phf_ktab k_log, double* z) {
+  const phf_u32x4 b = phf_philox_mh_t_uniform(chain_id, problem_id, t, seed_lo, seed_hi, seed_lo_u, seed_hi_w1_u);
+  return phf_mh_draws_of_block(d, b, k_log, z);
+}
+PHF_HD uint32_t phf_mh_draws_w3_uniform(uint32_t chain_id, uint32_t problem_id, uint32_t t, uint32_t seed_lo, uint32_t seed_hi,
+                                        uint32_t seed_lo_u, uint32_t seed_hi_w1_u, double* z) {
+  const phf_u32x4 b = phf_philox_mh_t_uniform(chain_id, problem_id, t, seed_lo, seed_hi, seed_lo_u, seed_hi_w1_u);
+  return phf_mh_draws_w3_of_block(b, z);
 }
 
 /* The Metropolis test  phf_log_pos_k(phf_unit_open32(w)) < x  of the d == 3 draws: the same answer for every w and every x (NaN, +-0,

@@ -69,6 +69,16 @@ __device__ __forceinline__ void chol_packed(const double* c, double* l) {
 #ifndef PHF_SL_STEADY_NOCLAMP
 #define PHF_SL_STEADY_NOCLAMP 1    // straight-line bodies without the Hill exponentials' lower clamp (run_block sends other pairs elsewhere)
 #endif
+// Round 11, wave-uniform work off the vector pipe (-DPHF_UNI_...=0 keeps the parent's form of a part)
+#ifndef PHF_UNI_PHILOX
+#define PHF_UNI_PHILOX 1           // two-wavefront steady bodies: Philox round 1's uniform word and round 2's product on the scalar unit
+#endif
+#ifndef PHF_UNI_TEMP0
+#define PHF_UNI_TEMP0 1            // straight-line bodies without the temperature-0 select (run_block sends such problems elsewhere)
+#endif
+#ifndef PHF_UNI_SLOT
+#define PHF_UNI_SLOT 1             // shared-denominator bodies: the LDS byte offsets of the shared slots computed once per call
+#endif
 // chol_packed for the steady bodies: the same operations without the pivots' selects, which change a value only where a pivot is not
 // positive.  The predicates stay (!(s > 0): a NaN pivot counts), and when ANY lane of the wavefront has such a pivot the guarded
 // version above runs and every lane that has one takes ITS whole factor.  A lane whose pivots are all positive has selected nothing
@@ -152,6 +162,10 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
   // the straight-line steady bodies run only pairs whose every ln_conc is >= PHF_LN_CONC_NOCLAMP (run_block) and drop the lower clamp of
   // the Hill exponentials (phf_sl_log_target_sampler); the run-time-loop body serves every pair and keeps it
   constexpr int kLowerClamp = !(PHF_SL_STEADY_NOCLAMP && STEADY && KO >= 0);
+  // ... and only problems whose temperature is neither +-0 nor NaN (run_block), and drop the select lik = 0 at temperature 0
+  constexpr int kTemp0Select = !(PHF_UNI_TEMP0 && STEADY && KO >= 0);
+  // the steady bodies of the two-wavefront build draw through phf_philox_mh_t_uniform (the general body keeps phf_philox_mh: the same words)
+  constexpr bool kUniPhilox = PHF_UNI_PHILOX && STEADY && !LONE_WAVE;
   const int C = a.prob.chains_per_problem;
   const int n_other = (KO >= 0) ? KO : n_other_rt;
   const int n_cens = (KC >= 0) ? KC : n_cens_rt;
@@ -169,6 +183,9 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
   // cost registers the scratch spills outside the loop absorb: C3 159.1 -> 158.0 ms per 8 000 iterations on one box, twice;
   // measured again after the table-driven functions (no scalar-memory fetches left to compete for SGPRs): 106.7 as scalars, 104.4
   // as vectors.  The lone-wavefront build keeps them scalar (round 2: scalar work is free there, vector issue slots are not).
+  // Two of the key words ALSO as scalars (phf_philox_mh_t_uniform): the first round's first word and the second round's second — two
+  // SGPRs, not twenty.
+  const uint32_t seed_lo_u = seed_lo, seed_hi_w1_u = seed_hi + 0xBB67AE85u;
   if (!LONE_WAVE) { asm volatile("" : "+v"(seed_lo)); asm volatile("" : "+v"(seed_hi)); }
   const size_t nchains = (size_t)a.prob.num_problems * C;
   const size_t g = (size_t)q * C + c;
@@ -225,6 +242,17 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
   uint32_t w_u = 0u;
   if constexpr (D == 3) w_u = phf_mh_draws_w3(cid, pid, (uint32_t)(t_begin + 1), seed_lo, seed_hi, z);
   else log_u = phf_mh_draws(D, cid, pid, (uint32_t)(t_begin + 1), seed_lo, seed_hi, k_log, z);
+  // Shared denominators: censored entry m reads slot den_off[m] of this lane, s_den[den_off[m] + lane].  The byte offset is the same for the
+  // whole call; hipcc rebuilds it every iteration from a spilled scalar (v_readlane_b32 + v_lshl_add_u32 per shared entry) unless it is
+  // handed over as a value it cannot look into.
+  int den_boff[kMaxShared];
+#pragma unroll
+  for (int m = 0; m < kMaxShared; ++m) {
+    den_boff[m] = (den_off[m] + (int)threadIdx.x) * (int)sizeof(double);
+    if (PHF_UNI_SLOT && STEADY && ((SHARE >> m) & 1u)) asm volatile("" : "+v"(den_boff[m]));
+  }
+  // the problem's number comes from a vector load (hipcc cannot prove the table unchanged by the stores of the general part): as a scalar
+  const uint32_t pid_u = kUniPhilox ? (uint32_t)__builtin_amdgcn_readfirstlane((int)pid) : pid;
   // Iteration bookkeeping in 32 bits (advance_impl refuses t_end > 0xffffffff): gfx950 has no scalar 64-bit ordering compare, so a
   // 64-bit t costs the vector pipe a copy and a v_cmp_*_i64 per test.  `left` counts down (t itself may end at 0xffffffff); the two
   // 64-bit thresholds become a 32-bit value and flags for the cases it cannot express, fixed before the loop.
@@ -251,9 +279,9 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
     double lik_star, prior_star, ll1_star, lt_star;
     bool inside = true;
     if constexpr (STEADY) {      // a proposal outside the prior's support is rejected by the predicate, not by a -inf (phf_model.h)
-      inside = !phf_sl_log_target_sampler(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature,
-                                          kLowerClamp, star, k_exp, k_log, SHARE, den_off, s_den + threadIdx.x, kBlock, &lik_star, &prior_star,
-                                          &ll1_star, &lt_star);
+      inside = !phf_sl_log_target_sampler_t(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature,
+                                            kLowerClamp, kTemp0Select, star, k_exp, k_log, SHARE, den_boff, s_den, s_den + threadIdx.x, kBlock,
+                                            &lik_star, &prior_star, &ll1_star, &lt_star);
     } else {
       phf_sl_log_target_shared(MODEL, lc, yv, wv, n_other, n_cens, n_other_points, ss_within, pi_bit, temperature, star, k_exp, k_log,
                                SHARE, den_off, s_den + threadIdx.x, kBlock, &lik_star, &prior_star, &ll1_star);
@@ -299,8 +327,13 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& a, const double*
     double z_next[3];
     double log_u_next = 0.0;
     uint32_t w_u_next = 0u;
-    if constexpr (D == 3) w_u_next = phf_mh_draws_w3(cid, pid, t + 1u, seed_lo, seed_hi, z_next);
-    else log_u_next = phf_mh_draws(D, cid, pid, t + 1u, seed_lo, seed_hi, k_log, z_next);
+    if constexpr (kUniPhilox) {
+      if constexpr (D == 3) w_u_next = phf_mh_draws_w3_uniform(cid, pid_u, t + 1u, seed_lo, seed_hi, seed_lo_u, seed_hi_w1_u, z_next);
+      else log_u_next = phf_mh_draws_uniform(D, cid, pid_u, t + 1u, seed_lo, seed_hi, seed_lo_u, seed_hi_w1_u, k_log, z_next);
+    } else {
+      if constexpr (D == 3) w_u_next = phf_mh_draws_w3(cid, pid, t + 1u, seed_lo, seed_hi, z_next);
+      else log_u_next = phf_mh_draws(D, cid, pid, t + 1u, seed_lo, seed_hi, k_log, z_next);
+    }
     if constexpr (STEADY && PHF_SL_STEADY_CHOL) chol_packed_steady<D>(cov, L);
     else chol_packed<D>(cov, L);
     sc = phf_exp_fast_k(0.5 * loga, k_exp);
@@ -413,7 +446,13 @@ __device__ __forceinline__ void run_block(const AdvanceArgs& a, double* s_pts, d
     for (int j = 0; j < n_other + n_cens; ++j) doses_bounded &= (int)(s_pts[j] >= PHF_LN_CONC_NOCLAMP);
     doses_bounded = __builtin_amdgcn_readfirstlane(doses_bounded);
   }
-  if (n_other <= 5 && n_cens <= 4 && doses_bounded) {
+  // Wave-uniform likewise: a problem at temperature +-0 or NaN takes the run-time-loop body, which keeps the select lik = 0 at temperature 0.
+  int temp_plain = 1;
+  if (PHF_UNI_TEMP0) {
+    const double temperature = a.prob.temperature[q];
+    temp_plain = __builtin_amdgcn_readfirstlane((int)(temperature != 0.0 && temperature == temperature));
+  }
+  if (n_other <= 5 && n_cens <= 4 && doses_bounded && temp_plain) {
     switch (n_other * 8 + n_cens) {                     // wave-uniform
       PHF_SHAPE_CASE(0, 1) PHF_SHAPE_CASE(0, 2) PHF_SHAPE_CASE(0, 3) PHF_SHAPE_CASE(0, 4)
       PHF_SHAPE_CASE(1, 0) PHF_SHAPE_CASE(1, 1) PHF_SHAPE_CASE(1, 2) PHF_SHAPE_CASE(1, 3) PHF_SHAPE_CASE_SHARED(1, 4, 0x8u)

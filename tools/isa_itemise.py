@@ -9,6 +9,10 @@ kernel in a hipcc -S listing — what the vector-ALU slots of an iteration are s
                                                                                ("crumb": weight the bodies by the Crumb set's pairs; reference.s:
                                                                                an earlier listing that names the bodies where the LDS reads cannot)
 
+    python tools/isa_itemise.py sl.s mh_advance_kernelILi2ELb0ELi2E uniform [reference.s]
+                                                                               (listing only, "round 11": per body the vector instructions whose
+                                                                               result is the same in all lanes or a constant — uniform_report)
+
 A loop = a backward branch whose span holds no other backward branch; classes by opcode (and, for Philox, by its constants).  A region
 that a forward s_cbranch_vccz skips and that reads LDS (the accept test's logarithm) or holds six or more selects (the guarded Cholesky
 factor of the steady bodies) is a rare path and is listed apart, not counted."""
@@ -137,7 +141,103 @@ def reference_shapes(path, want):
     return {k: next(iter(v)) for k, v in found.items() if len(v) == 1 and None not in v}
 
 
+def rare_regions(ins, labels, a, b):
+    """instruction indices of body [a..b] that a forward s_cbranch_vccz skips and that read LDS or hold six or more selects (main)"""
+    skip = set()
+    for i in range(a, b):
+        m = re.match(r"s_cbranch_vccz (\.LBB\d+_\d+)", ins[i])
+        if m and m.group(1) in labels and i < labels[m.group(1)] <= b:
+            region = range(i + 1, labels[m.group(1)])
+            if any(ins[j].startswith("ds_read") for j in region) or sum(ins[j].startswith("v_cndmask") for j in region) >= 6:
+                skip.update(region)
+    return skip
+
+
+def _operands(line):
+    parts = line.split(None, 1)
+    return [o.strip() for o in parts[1].split(",")] if len(parts) > 1 else []
+
+
+def _vector_registers(operand):
+    """the VGPRs and AGPRs an operand names, as ("v" | "a", number)"""
+    regs = set()
+    for kind, one, lo, hi in re.findall(r"\b([va])(?:(\d+)\b|\[(\d+):(\d+)\])", operand):
+        regs.update((kind, r) for r in (range(int(one), int(one) + 1) if one else range(int(lo), int(hi) + 1)))
+    return regs
+
+
+def _destinations(line):
+    """how many leading operands an instruction WRITES: none for stores, LDS writes, scalar instructions and the e32 compares (vcc is
+    implied there but written first in the text, and names no vector register anyway); two for the carry-out and 64-bit multiply-add forms"""
+    op = line.split()[0]
+    if re.match(r"(ds_write|global_store|buffer_store|scratch_store|global_atomic|s_|v_cmpx)", op):
+        return 0
+    if re.match(r"v_(mad_[ui]64_[ui]32|add_co|sub_co|subrev_co|addc_co|subb_co|subbrev_co|div_scale)", op):
+        return 2
+    return 1
+
+
+def uniform_report(ins, labels, inner, name_of):
+    """Per iteration body: the VALU instructions none of whose vector-register sources is written anywhere inside the loop (rare paths
+    included) — every such source is loop invariant, so the result can vary from iteration to iteration only through scalar registers,
+    which hold one value for the whole wavefront, or not at all (a constant).  An instruction that accumulates into its destination
+    (v_fmac, v_mac, v_writelane) reads it.  These are candidates, not verdicts: a loop-invariant VGPR may still differ from lane to lane
+    (then the result is not wave-uniform and the instruction is simply hoistable or needed), and a move under the accept mask writes a
+    constant into SOME lanes.  One step further, marked "derived": walking the body in order, a register whose current value was written
+    from scalar registers, constants and such registers alone — by a vector instruction, or by a global_load at such an address (the
+    gamma table's entry) — holds a wave-uniform value, and counts as no varying source for the instructions behind it, up to its next
+    write by anything else.  (A loop-invariant VGPR passes nothing on — it may hold the chain's number — unless the nearest instruction
+    in front of the loop that writes it is a move of a constant or of a scalar register: the zero offset of the gamma load.)  What is
+    decided about each is in DESIGN.md section 3, "round 11"."""
+    for a, b in sorted(inner, key=lambda ab: (sum(1 for l in ins[ab[0]:ab[1] + 1] if l.startswith("v_")), ab)):
+        written = set()
+        for l in ins[a:b + 1]:
+            ops = _operands(l)
+            for o in ops[:_destinations(l)]:
+                written |= _vector_registers(o)
+        rare = rare_regions(ins, labels, a, b)
+        found = []
+        derived = set()                                        # registers whose current value comes from SGPRs, constants and such registers alone
+        pending = {r for l in ins[a:b + 1] for o in _operands(l)[_destinations(l):] for r in _vector_registers(o)} - written
+        for i in range(a - 1, max(a - 20000, -1), -1):          # loop-invariant sources: what set them in front of the loop
+            if not pending:
+                break
+            ops = _operands(ins[i])
+            hit = pending & (set().union(*[_vector_registers(o) for o in ops[:_destinations(ins[i])]]) if _destinations(ins[i]) else set())
+            if hit:
+                pending -= hit
+                if re.match(r"v_mov_b(32|64)", ins[i]) and not _vector_registers(ops[1]):
+                    derived |= hit
+        for i in range(a, b + 1):
+            l = ins[i]
+            ops = _operands(l)
+            nd = _destinations(l)
+            dst = set().union(*[_vector_registers(o) for o in ops[:nd]]) if nd else set()
+            sources = ops[nd:]
+            if re.match(r"v_(fmac|mac|pk_fmac|writelane)", l):
+                sources = sources + ops[:1]
+            vsrc = set().union(*[_vector_registers(o) for o in sources]) if sources else set()
+            if (l.startswith("v_") or l.startswith("global_load")) and not (vsrc & written) - derived:
+                if l.startswith("v_"):
+                    scalar = any(re.search(r"\b(s\d+|s\[|vcc|exec|m0|ttmp)", o) for o in sources)
+                    kind = ("invariant VGPRs + SGPR" if vsrc and scalar else "invariant VGPRs only" if vsrc else "SGPR only" if scalar else "constant")
+                    found.append((i, kind + (", derived" if vsrc & derived else ""), l))
+            if (l.startswith("v_") or l.startswith("global_load")) and vsrc <= derived:
+                derived |= dst
+            else:
+                derived -= dst
+        counted = [f for f in found if f[0] not in rare]
+        shape = name_of(ins[a:b + 1])
+        print("\n  body [%d..%d]%s: %d candidates, %d issue cycles (another %d on a rare path)" % (
+            a, b, "" if shape is None else " = %d uncensored + %d censored entries%s" % (shape[0], shape[1], ", shared denominators" if shape[2] else ""),
+            len(counted), sum(issue_cycles(l) for _, _, l in counted), len(found) - len(counted)))
+        for i, kind, l in found:
+            print("     +%-4d %-33s %s%s" % (i - a, kind, " ".join(l.split()), "   (rare path)" if i in rare else ""))
+
+
 def main():
+    if len(sys.argv) > 3 and sys.argv[3] == "uniform":
+        return main_uniform()
     src = open(sys.argv[1]).read().split("\n")
     want = sys.argv[2]
     reference = reference_shapes(sys.argv[4], want) if len(sys.argv) > 4 else {}
@@ -264,6 +364,32 @@ def main():
             print("     issue cycles of the vector pipe per wavefront and iteration (measured cost per instruction: tools/isa_instr_cost.py): %.0f" % (sum(cyc_tot.values()) / wsum))
             for k_, v in sorted(cyc_tot.items(), key=lambda kv: -kv[1]):
                 print("     %7.0f  %s" % (v / wsum, k_))
+
+
+def main_uniform():
+    src = open(sys.argv[1]).read().split("\n")
+    want = sys.argv[2]
+    reference = reference_shapes(sys.argv[4], want) if len(sys.argv) > 4 else {}
+    starts = [i for i, l in enumerate(src) if re.match(r"_Z\w+:", l)]
+    for si, s0 in enumerate(starts):
+        name = src[s0].split(":", 1)[0]
+        if want not in name:
+            continue
+        labels, ins = {}, []
+        for l in src[s0 + 1:starts[si + 1] if si + 1 < len(starts) else len(src)]:
+            l = l.strip()
+            m = re.match(r"(\.LBB\d+_\d+):", l)
+            if m:
+                labels[m.group(1)] = len(ins)
+            elif l.startswith(".Lfunc_end"):
+                break
+            elif l and not l.startswith(";") and not l.startswith("."):
+                ins.append(l)
+        back = [(labels[m.group(1)], i) for i, l in enumerate(ins) for m in [re.match(r"s_cbranch_\w+ (\.LBB\d+_\d+)", l)]
+                if m and m.group(1) in labels and labels[m.group(1)] <= i]
+        inner = [(a, b) for a, b in back if b - a > 300 and not any(a <= c and d <= b and (c, d) != (a, b) for c, d in back)]
+        print("%s: %d instructions, %d iteration bodies; wave-uniform / constant candidates per body" % (name, len(ins), len(inner)))
+        uniform_report(ins, labels, inner, (lambda body: reference.get(shape_key(body))) if reference else shape_by_lds)
 
 
 if __name__ == "__main__":
