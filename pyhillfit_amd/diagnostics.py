@@ -13,7 +13,8 @@ accumulates every half-chain's mean and autocovariance acov(k), k = 0..L, L = mi
     (P_t <- min(P_t, P_t-1)),  tau = max(-1 + 2 sum_t P_t, 1/log10(M h)),  ESS = M h / tau,  MCSE = sqrt(var+/ESS).
 
 ESS and MCSE are NaN (null in JSON) when the sequence has not turned non-positive by lag L < h-1 (lag_limit_reached: a cut there
-would overstate the ESS) and, with R-hat, when W = 0 (a column that never moved).  When L = h-1 and the sequence never turns, every
+would overstate the ESS) and, with R-hat, when W = 0 (a column that never moved) or W is not finite (a value that is not finite in
+the column); json_record() then names the cause per column under "reason".  When L = h-1 and the sequence never turns, every
 available pair P_t (2t+1 <= L) is kept."""
 import ctypes as C
 
@@ -28,6 +29,7 @@ DEFAULT_LAGS = 256
 RHAT_THRESHOLD = 1.01
 METHOD = ("split-R-hat and multi-chain ESS (Stan reference manual; Geyer initial positive + monotone sequence) without rank "
           "normalisation; MCSE of the mean = sqrt(var+/ESS)")
+UNDETERMINED = "W is not positive: the column never moved within a half-chain (0/0), or it holds a value that is not finite"
 
 
 def effective_lags(total_rows, lags=DEFAULT_LAGS):
@@ -151,6 +153,8 @@ def json_record(res, q, lags, total_rows, chains, columns=None):
            "lags": int(lags), "rows_per_half_chain": int(total_rows) // 2, "half_chains": 2 * int(chains), "method": METHOD}
     if columns is not None:
         rec["columns"] = list(columns)
+    if any(v is None for v in rec["rhat"]):
+        rec["reason"] = [UNDETERMINED if v is None else None for v in rec["rhat"]]
     return rec
 
 
