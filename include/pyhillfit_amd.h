@@ -822,6 +822,36 @@ int phf_design_accumulate(int model, int bins, const double* rows, int64_t num_r
                           int num_chains, int64_t first_row, int every, const double* ln_doses, int num_doses, int num_slots,
                           double* accumulators, size_t accumulator_bytes, void* stream);
 
+/* ---- Savage-Dickey Bayes factor B12 of "Hill = 1" (model 1) against "Hill free" (model 2) -------------------------------------
+ * (pyhillfit_amd/csrc/phf_savage_dickey.hip, phf_savage_dickey.h; DESIGN.md §3, "Savage-Dickey Bayes factor").  From the t = 1 draws
+ * of the MODEL-2 fit alone — what python/compute_bayes_factors.py:11-27 reaches through a 41-rung tempered ladder per pair and model:
+ * B12 = p(Hill = 1 | y, M2) / pi(Hill = 1 | M2) = the posterior mean of
+ *   r = L(pIC50, 1, sigma) / ((1/10) INT_0^10 L(pIC50, h, sigma) dh),
+ * the integral by a fixed rule at the draw's (pIC50, sigma): [0, 10] in `panels` equal panels, the 15-point Gauss-Kronrod rule on
+ * each (fine), its 7 embedded Gauss nodes (coarse).  The draw's Hill column is not read.  Valid only while model 1 is model 2 at
+ * Hill = 1 with the same priors on pIC50 and sigma and a uniform prior on Hill (asserted in phf_savage_dickey.h).
+ *   pts           the sampler's merged entries, pair q <-> problem q (pi_bit and extra are not read); stride <= 256
+ *   panels        16, 32 or 64
+ *   nodes         device [3][15 panels] doubles: h_k, ln w_k (fine), ln w_k (coarse, -inf at the nodes that are no Gauss nodes),
+ *                 made on the host (pyhillfit_amd/savage_dickey.py: node_table)
+ *   rows          device [num_rows][num_problems][4][num_chains], model-2 rows (pIC50, Hill, sigma, log-target): row_stride_cols must
+ *                 be 4; rows[0] is global post-burn-in row first_row, and exactly the global rows r with r mod every == 0 are used,
+ *                 however the calls cut the rows
+ *   accumulators  device [num_problems][num_chains][8] doubles, zeroed by the caller before the first call and updated in place:
+ *                 draws used, draws skipped, SUM r_fine, SUM r_fine^2, max r_fine, SUM r_coarse, max |log r_fine - log r_coarse|, 0
+ * A draw with sigma <= 1e-3, or whose pIC50 or sigma is not finite, is skipped and counted.  Every sum is a plain left-to-right sum
+ * over the chain's used rows in row order that starts from the stored value: the same rows and the same `every` give the same bits
+ * however the calls cut them, bit-identical to the host build of phf_savage_dickey.h.  No atomics; nothing is merged across chains.
+ * A call that holds no used row launches nothing.  Every argument is checked before any launch: PHF_ERR_INVALID_ARGUMENT without
+ * touching a GPU (phf_last_error() says why). */
+int phf_savage_dickey_accumulator_doubles(void);   /* 8 */
+int phf_savage_dickey_nodes(int panels);           /* 15 panels; -1 for a panel count that is not allowed */
+/* the number of rows r in [first_row, first_row + num_rows) with r mod every == 0 (-1 for an invalid argument) */
+int64_t phf_savage_dickey_rows_used(int64_t first_row, int64_t num_rows, int every);
+int phf_savage_dickey_accumulate(const phf_points* pts, int panels, const double* nodes, const double* rows, int64_t num_rows,
+                                 int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int every,
+                                 double* accumulators, size_t accumulator_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

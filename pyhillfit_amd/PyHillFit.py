@@ -10,6 +10,7 @@
            [--sensitivity [--sensitivity-delta 0.01] [--sensitivity-bins 4096] [--sensitivity-threshold 0.05]]
            [--hierarchical --de-every K [--de-population 64] [--de-gamma GAMMA] [--de-jump-every 10]]
            [--next-dose G [--next-dose-concs c1,c2,...] [--next-dose-bins 256] [--next-dose-every 17]] [--correlations]
+           [-m 2 --savage-dickey [--savage-dickey-panels 32] [--savage-dickey-every 11]]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -31,7 +32,9 @@ predicted future experiment at G doses (and at the named --band-concs), accumula
 accumulated the same way and written to the summary JSON as "sensitivity"; with --next-dose G (single-level), the expected information
 gain of one further measurement at G candidate doses (pyhillfit_amd/design.py), accumulated the same way and written as "next_dose"; with --correlations, the posterior and within-chain correlation matrices of the
 parameter columns and the multivariate R-hat with the direction along which the chains sit apart (pyhillfit_amd/correlations.py),
-accumulated the same way and written as "correlations".  The CMA-ES start point is replaced by a deterministic least-squares fit
+accumulated the same way and written as "correlations"; with -m 2 --savage-dickey, the Bayes factor B12 of Hill = 1 against Hill free by
+the Savage-Dickey density ratio from this run's draws alone (pyhillfit_amd/savage_dickey.py), accumulated the same way and written as
+"bayes_factor".  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -139,6 +142,22 @@ def check_args(parser, args):
         args.next_dose_every = ds.DEFAULT_EVERY if args.next_dose_every is None else args.next_dose_every
         if args.next_dose_every < 1:
             parser.error("--next-dose-every must be >= 1")
+    sd_given = [n for n in ("savage_dickey_panels", "savage_dickey_every") if getattr(args, n, None) is not None]
+    if sd_given and not args.savage_dickey:
+        parser.error("--%s needs --savage-dickey" % sd_given[0].replace("_", "-"))
+    if args.savage_dickey:
+        if args.hierarchical:
+            parser.error("--savage-dickey is single-level only: the hierarchical model has no Hill = 1 sub-model with nested priors")
+        if args.model != 2:
+            parser.error("--savage-dickey needs -m 2: B12 is read off the Hill-free fit (model 1 is model 2 at Hill = 1)")
+        from . import savage_dickey as sd
+        try:
+            args.savage_dickey_panels = sd.check_panels(sd.DEFAULT_PANELS if args.savage_dickey_panels is None else args.savage_dickey_panels)
+        except ValueError as e:
+            parser.error(str(e))
+        args.savage_dickey_every = sd.DEFAULT_EVERY if args.savage_dickey_every is None else args.savage_dickey_every
+        if args.savage_dickey_every < 1:
+            parser.error("--savage-dickey-every must be >= 1")
     de_given = [n for n in ("de_population", "de_gamma", "de_jump_every") if getattr(args, n, None) is not None]
     if args.de_every < 0:
         parser.error("--de-every must be >= 0 (0 = no differential-evolution moves)")
@@ -250,6 +269,16 @@ def build_parser():
                      "1998, in the convention of the split-R-hat) with the linear combination of the parameters along which the chains "
                      "disagree most, from co-moments accumulated on the GPU while the rows stream past; written to the summary JSON as "
                      "\"correlations\"")
+    new.add_argument("--savage-dickey", action='store_true', default=False, help="-m 2 only: the Bayes factor B12 of Hill = 1 (model 1) against "
+                     "Hill free (model 2) by the Savage-Dickey density ratio, from this run's draws alone (no tempered ladder, no model-1 "
+                     "fit): the mean over the draws of L(Hill = 1) / mean over Hill's prior of L, the latter by Gauss-Kronrod quadrature "
+                     "on the GPU while the rows stream past; valid for the nested priors of models 1 and 2 only; written to the summary "
+                     "JSON as \"bayes_factor\"")
+    new.add_argument("--savage-dickey-panels", type=int, default=None, metavar="P", help="--savage-dickey: equal panels of [0, 10], each with "
+                     "the 15-point Gauss-Kronrod rule: 16, 32 (default) or 64; raise it when pairs are reported with a quadrature gap")
+    new.add_argument("--savage-dickey-every", type=int, default=None, metavar="T", help="--savage-dickey: every T-th post-burn-in row of every "
+                     "chain is used (default 11: on the whole Crumb set at the default chains and P = 32 the flag then adds no more than the "
+                     "sampling time; the cost grows with P / T)")
     new.add_argument("--de-every", type=int, default=0, metavar="K", help="--hierarchical: differential-evolution moves between the chains of "
                      "each pair (ter Braak 2006) after every K iterations, K a multiple of the thinning (default 0 = off: every output as "
                      "without the flag); the chains of one population are then coupled; written to the summary JSON as \"de_moves\"")

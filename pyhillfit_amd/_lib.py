@@ -30,7 +30,8 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_sensitivity_accumulate", "phf_sensitivity_reduce", "phf_sensitivity_components", "phf_batch_means_workspace_bytes",
            "phf_batch_means_levels", "phf_batch_means_init", "phf_batch_means_accumulate", "phf_batch_means_reduce",
            "phf_design_accumulator_doubles", "phf_design_rows_used", "phf_design_accumulate", "phf_comoments_workspace_bytes",
-           "phf_comoments_init", "phf_comoments_accumulate", "phf_comoments_reduce"]
+           "phf_comoments_init", "phf_comoments_accumulate", "phf_comoments_reduce", "phf_savage_dickey_accumulator_doubles",
+           "phf_savage_dickey_nodes", "phf_savage_dickey_rows_used", "phf_savage_dickey_accumulate"]
 
 
 class PhfError(RuntimeError):
@@ -183,6 +184,10 @@ def load():
     lib.phf_comoments_init.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp]
     lib.phf_comoments_accumulate.argtypes = [vp, i64, i32, i32, i32, i32, i64, i64, vp, C.c_size_t, vp]
     lib.phf_comoments_reduce.argtypes = [i32, i32, i32, i64, vp, C.c_size_t, vp, vp]
+    lib.phf_savage_dickey_nodes.argtypes = [i32]
+    lib.phf_savage_dickey_rows_used.argtypes = [i64, i64, i32]
+    lib.phf_savage_dickey_rows_used.restype = i64
+    lib.phf_savage_dickey_accumulate.argtypes = [C.POINTER(Points), i32, vp, vp, i64, i32, i32, i32, i64, i32, vp, C.c_size_t, vp]
     _lib = lib
     return lib
 

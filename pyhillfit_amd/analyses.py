@@ -30,6 +30,7 @@ from . import ppc as pp
 from . import predictive
 from . import quantiles as qn
 from . import replica_exchange as rx
+from . import savage_dickey as sd
 from . import sensitivity as sn
 from . import stepping_stone as ss
 from . import waic as wc
@@ -344,12 +345,27 @@ class Correlations(Analysis):
             summ["correlations"]["note"] = de.COUPLING_NOTE.format(G=run.de.G)
 
 
+class SavageDickeyBF(Analysis):
+    """--savage-dickey: the Bayes factor B12 of Hill = 1 against Hill free from the model-2 draws alone (single-level, -m 2 only)"""
+    what, module = "--savage-dickey", sd
+    hint = "accumulators, {:.1f} GB are free: select fewer pairs or fewer chains"
+
+    def make(self, run):
+        a = run.args
+        self.check(sd.workspace_bytes(run.Q, run.C, a.savage_dickey_panels))
+        return sd.SavageDickey(run.sampler_points, run.Q, run.C, a.savage_dickey_panels, a.savage_dickey_every, run.device)
+
+    def record(self, summ, q):
+        summ["bayes_factor"] = sd.json_record(self.res[q])
+
+
 def fit_analyses(args):
     """the analyses of a PyHillFit run, single-level or hierarchical, in the order they are built, fed, recorded and reported"""
     table = [(args.hierarchical and args.predictive_cdfs, PredictiveCdfs), (args.diagnostics, Diagnostics),
              (args.diagnostic_batch_means, BatchMeans), (args.de_every, DeMoves), (args.waic, Waic), (args.loo, Loo),
              (args.leave_experiment_out, ExperimentLoo), (args.quantiles, Quantiles), (args.ppc, Ppc), (args.sensitivity, Sensitivity),
-             (args.next_dose and not args.hierarchical, Design), (args.correlations, Correlations)]
+             (args.next_dose and not args.hierarchical, Design), (args.correlations, Correlations),
+             (args.savage_dickey and not args.hierarchical, SavageDickeyBF)]
     return [kind for on, kind in table if on]
 
 

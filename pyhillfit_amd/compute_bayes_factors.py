@@ -13,7 +13,10 @@ with the HIP batch evaluator (phf_single_level_log_target) instead of the Python
 --estimator stepping-stone takes log Z and its standard error from the "stepping_stone" object PyHillTemp --stepping-stone wrote
 (pyhillfit_amd/stepping_stone.py) and prints log B12 +- se; with --from-files it computes chain 0's stepping-stone estimate from the
 rung chain files (no standard error: one chain).  The se is the between-chain Monte Carlo error of the runs: it cannot see a bias
-that all chains of a rung share, and on the G6 setup the estimate's real error is far larger ("phf_stepping_stone.hip")."""
+that all chains of a rung share, and on the G6 setup the estimate's real error is far larger ("phf_stepping_stone.hip").
+
+--estimator savage-dickey needs no ladder: it reads the "bayes_factor" object PyHillFit -m 2 --savage-dickey wrote into the pair's
+model-2 summary (pyhillfit_amd/savage_dickey.py) and prints log B12 +- se."""
 import argparse
 import json
 import os
@@ -93,6 +96,35 @@ def stepping_stone_main(args, top_drug, top_channel, concs, responses, temps):
             "log_B12_se": log_b12_se, "estimator": "stepping-stone", "se_methods": methods}
 
 
+def savage_dickey_main(args, top_drug, top_channel):
+    """--estimator savage-dickey: log B12 and its se from the "bayes_factor" object PyHillFit -m 2 --savage-dickey wrote into the
+    pair's model-2 summary; no ladder and no model-1 fit"""
+    dr.define_model(2)
+    drug, channel, chain_file, _ = dr.nonhierarchical_chain_file_and_figs_dir(2, top_drug, top_channel, 1)
+    summary = chain_file[:-4] + "_summary.json"
+    run = "run PyHillFit -m 2 --savage-dickey --drugs {} --channels {} first".format(top_drug, top_channel)
+    if not os.path.exists(summary):
+        raise SystemExit("%s is missing: %s" % (summary, run))
+    with open(summary) as f:
+        rec = json.load(f).get("bayes_factor")
+    if rec is None:
+        raise SystemExit("%s has no Savage-Dickey Bayes factor: %s" % (summary, run))
+    if rec["log_b12"] is None:
+        raise SystemExit("%s: the Bayes factor is not finite (%s)" % (summary, rec.get("reason")))
+    log_b12, se = float(rec["log_b12"]), rec["log_b12_se"]
+    print("log B12 = {:.6g} +- {}".format(log_b12, "n/a (one chain)" if se is None else
+                                          "{:.3g} (between-chain Monte Carlo error only)".format(se)))
+    if not rec["reliable"]:
+        print("not reliable: {}".format(rec.get("reason")))
+    if not os.path.exists(args.bf_dir):
+        os.makedirs(args.bf_dir)
+    bf_file = args.bf_dir + "{}_{}_B12.txt".format(drug, channel)
+    B12 = np.exp(log_b12)
+    np.savetxt(bf_file, [B12])
+    return {"B12": float(B12), "sources": {2: "savage-dickey"}, "file": bf_file, "log_B12": log_b12, "log_B12_se": se,
+            "estimator": "savage-dickey", "reliable": bool(rec["reliable"])}
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(prog="compute_bayes_factors.py")
     parser.add_argument("-nc", "--num-cores", type=int, default=1, help="accepted for compatibility")
@@ -106,14 +138,17 @@ def main(argv=None):
     new.add_argument("--device", type=str, default="cuda:0")
     new.add_argument("--output-root", type=str, default="output")
     new.add_argument("--bf-dir", type=str, default="BFs/")
-    new.add_argument("--estimator", choices=("ti", "stepping-stone"), default="ti",
-                     help="ti: thermodynamic integration (the reference's); stepping-stone: PyHillTemp --stepping-stone's log Z with its se")
+    new.add_argument("--estimator", choices=("ti", "stepping-stone", "savage-dickey"), default="ti",
+                     help="ti: thermodynamic integration (the reference's); stepping-stone: PyHillTemp --stepping-stone's log Z with its se; "
+                          "savage-dickey: the \"bayes_factor\" PyHillFit -m 2 --savage-dickey wrote (no ladder)")
     if argv is None and len(sys.argv) == 1:
         parser.print_help(); sys.exit(1)
     args = parser.parse_args(argv)
     dr.setup(args.data_file)
     dr.output_root = args.output_root
     top_drug, top_channel = dr.drugs[args.drug], dr.channels[args.channel]                 # :50-51
+    if args.estimator == "savage-dickey":
+        return savage_dickey_main(args, top_drug, top_channel)
     num_expts, _, experiments = dr.load_crumb_data(top_drug, top_channel)
     concs, responses = dr.concatenate_experiments(num_expts, experiments)                  # :55-59
     temps = dr.temperature_ladder(args.rungs)                                              # :70
