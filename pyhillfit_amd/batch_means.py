@@ -23,7 +23,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
@@ -44,11 +44,7 @@ def levels(total_rows):
 
 def workspace_bytes(num_problems, columns, chains, total_rows):
     """device bytes BatchMeans holds: num_problems * columns * chains * (5 NL + 2) doubles (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_batch_means_workspace_bytes(int(num_problems), int(columns), int(chains), int(total_rows))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_batch_means_workspace_bytes", num_problems, columns, chains, total_rows)
 
 
 def finalize(reduced, h, num_half_chains):
@@ -88,40 +84,23 @@ def finalize(reduced, h, num_half_chains):
             "ess_upper_bound": bound}
 
 
-class BatchMeans(object):
+class BatchMeans(accumulator.RowAccumulator):
     """Streaming batch means of num_problems x columns over `chains` chains and total_rows post-burn-in rows, used like
     diagnostics.ChainDiagnostics: accumulate() takes the rows in order, a segment at a time, as views of the sampler's row buffer
     [rows][Q][stride][chains] (asynchronous, on the current stream); result() reduces and finalizes."""
 
     def __init__(self, num_problems, chains, columns, total_rows, device="cuda"):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("BatchMeans runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         self.Q, self.C, self.cols, self.N = int(num_problems), int(chains), int(columns), int(total_rows)
-        self.nbytes = workspace_bytes(self.Q, self.cols, self.C, self.N)
+        self.min_cols = self.cols
         self.h = self.N // 2
         self.nl = levels(self.N)
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_batch_means_init(self.Q, self.cols, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                                 _stream_ptr(self.device)), "phf_batch_means_init")
-        self.rows_seen = 0
+        self._init_workspace(workspace_bytes(self.Q, self.cols, self.C, self.N), "phf_batch_means_init", self.Q, self.cols, self.C, self.N)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         _lib.check(self.lib.phf_batch_means_accumulate(_ptr(rows), n, self.Q, rows.shape[2], self.C, self.cols, self.rows_seen, self.N,
                                                        _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
                    "phf_batch_means_accumulate")
-        self.rows_seen += n
 
     def workspace(self):
         """the device state as numpy [Q][cols][5 NL + 2][C] (include/pyhillfit_amd.h names the fields)"""
@@ -129,8 +108,7 @@ class BatchMeans(object):
 
     def reduced(self):
         """[Q][cols][NL+1] numpy: what phf_batch_means_reduce writes"""
-        if self.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.rows_seen, self.N))
+        self._check_complete()
         out = torch.empty((self.Q, self.cols, self.nl + 1), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.phf_batch_means_reduce(self.Q, self.cols, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _ptr(out),
                                                    _stream_ptr(self.device)), "phf_batch_means_reduce")
@@ -139,9 +117,6 @@ class BatchMeans(object):
     def result(self):
         """finalize()'s dict, arrays [Q][cols]"""
         return finalize(self.reduced(), self.h, 2 * self.C)
-
-    def free(self):
-        self.ws = None
 
 
 def diagnose(chains, device="cuda"):

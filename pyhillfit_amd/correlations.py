@@ -33,7 +33,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
@@ -59,11 +59,7 @@ def out_doubles(d):
 
 def workspace_bytes(num_problems, columns, chains, total_rows):
     """device bytes PosteriorCorrelations holds: num_problems * 2 * chains * fields(columns) doubles (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_comoments_workspace_bytes(int(num_problems), int(columns), int(chains), int(total_rows))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_comoments_workspace_bytes", num_problems, columns, chains, total_rows)
 
 
 def unpack(reduced, d):
@@ -140,40 +136,23 @@ def finalize(W, Bh, mean, m, h, dropped=0, columns=None):
     return res
 
 
-class PosteriorCorrelations(object):
+class PosteriorCorrelations(accumulator.RowAccumulator):
     """Streaming co-moments of num_problems problems over `chains` chains, the d = len(columns) leading columns of a row and
     total_rows post-burn-in rows.  accumulate() takes the rows in order, a segment at a time, as views of the sampler's row buffer
     [rows][Q][stride][chains] (asynchronous, on the current stream); result() reduces and finalizes, per problem."""
 
     def __init__(self, num_problems, chains, columns, total_rows, device="cuda"):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PosteriorCorrelations runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         self.columns = ["column_%d" % i for i in range(columns)] if isinstance(columns, int) else list(columns)
         self.Q, self.C, self.d, self.N = int(num_problems), int(chains), len(self.columns), int(total_rows)
-        self.nbytes = workspace_bytes(self.Q, self.d, self.C, self.N)
+        self.min_cols = self.d
         self.h = self.N // 2
-        self.ws = torch.empty(self.nbytes // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_comoments_init(self.Q, self.d, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                               _stream_ptr(self.device)), "phf_comoments_init")
-        self.rows_seen = 0
+        self._init_workspace(workspace_bytes(self.Q, self.d, self.C, self.N), "phf_comoments_init", self.Q, self.d, self.C, self.N)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= d][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.d:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.d, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         _lib.check(self.lib.phf_comoments_accumulate(_ptr(rows), n, self.Q, rows.shape[2], self.C, self.d, self.rows_seen, self.N,
                                                      _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
                    "phf_comoments_accumulate")
-        self.rows_seen += n
 
     def workspace(self):
         """the state as numpy [Q][2][fields(d)][C] (phf_comoments.h)"""
@@ -181,8 +160,7 @@ class PosteriorCorrelations(object):
 
     def reduced(self):
         """[Q][out_doubles(d)] numpy: W | B/h (upper triangles) | grand mean | shifted sums of means | m | dropped | h | 0"""
-        if self.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.rows_seen, self.N))
+        self._check_complete()
         out = torch.empty((self.Q, out_doubles(self.d)), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.phf_comoments_reduce(self.Q, self.d, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _ptr(out),
                                                  _stream_ptr(self.device)), "phf_comoments_reduce")
@@ -191,9 +169,6 @@ class PosteriorCorrelations(object):
     def result(self):
         """per problem, finalize()'s dict"""
         return [finalize_reduced(r, self.d, self.columns) for r in self.reduced()]
-
-    def free(self):
-        self.ws = None
 
 
 def finalize_reduced(reduced, d, columns=None):

@@ -15,7 +15,7 @@
 
 #include "../../include/pyhillfit_amd.h"
 #include "phf_batch_means.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_device_util.h"
 
 namespace {
@@ -93,22 +93,14 @@ __global__ __launch_bounds__(kThreads) void batch_means_reduce_kernel(const BmAr
 
 // shared argument checks of the four entries; on success *nl = floor(log2 h) + 1
 int check_shape(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows, int* nl) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || num_columns < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems, num_columns and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 4) {
-    std::snprintf(msg, sizeof msg, "%s: a half-chain needs h = floor(total_rows / 2) >= 2 rows (total_rows = %lld)", who, (long long)total_rows);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  int rc = phf_check_positive(who, "num_problems, num_columns and num_chains", {num_problems, num_columns, num_chains});
+  if (rc != PHF_OK) return rc;
+  if (total_rows < 4)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: a half-chain needs h = floor(total_rows / 2) >= 2 rows (total_rows = %lld)", who,
+                     (long long)total_rows);
   *nl = phf_bm_levels(total_rows / 2);
   const double units = (double)num_problems * num_columns * ((num_chains + 63) / 64 > *nl ? (num_chains + 63) / 64 : *nl);
-  if (units / kWaves > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
+  return phf_check_grid(who, {units / kWaves});
 }
 
 size_t workspace_bytes_of(int num_problems, int num_columns, int num_chains, int nl) {
@@ -130,15 +122,12 @@ extern "C" int phf_batch_means_levels(int64_t total_rows) {
 
 extern "C" int phf_batch_means_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, double* workspace,
                                     size_t workspace_bytes, void* stream) {
+  static const char* who = "phf_batch_means_init";
   int nl;
-  int rc = check_shape("phf_batch_means_init", num_problems, num_columns, num_chains, total_rows, &nl);
+  const int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows, &nl);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_init: null workspace");
   const size_t need = workspace_bytes_of(num_problems, num_columns, num_chains, nl);
-  if (workspace_bytes < need) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_init: workspace smaller than phf_batch_means_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_batch_means_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch("phf_batch_means_init");
-  return PHF_OK;
+  return phf_init_workspace(who, "batch_means", workspace, workspace_bytes, need, need, stream);
 }
 
 extern "C" int phf_batch_means_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
@@ -148,13 +137,11 @@ extern "C" int phf_batch_means_accumulate(const double* rows, int64_t num_rows, 
   int nl;
   int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows, &nl);
   if (rc != PHF_OK) return rc;
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
-  if (row_stride_cols < num_columns)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: row_stride_cols must be >= num_columns");
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
+  if ((rc = phf_check_row_stride(who, row_stride_cols, num_columns, "must be >= num_columns")) != PHF_OK) return rc;
   if (!rows || !workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains, nl))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_accumulate: workspace smaller than phf_batch_means_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "batch_means", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_columns, num_chains, nl))) != PHF_OK)
+    return rc;
   if (num_rows == 0) return PHF_OK;
   BmArgs a = {};
   a.Q = num_problems; a.stride = row_stride_cols; a.C = num_chains; a.cols = num_columns; a.nl = nl; a.ws = workspace;
@@ -162,14 +149,11 @@ extern "C" int phf_batch_means_accumulate(const double* rows, int64_t num_rows, 
   a.ncg = (num_chains + 63) / 64;
   a.units = (int64_t)num_problems * num_columns * a.ncg;
   const size_t row_doubles = (size_t)num_problems * row_stride_cols * num_chains;
-  const int64_t half_begin[2] = {0, total_rows - a.h};
   for (int half = 0; half < 2; ++half) {
-    const int64_t lo = first_row > half_begin[half] ? first_row : half_begin[half];
-    const int64_t end = first_row + num_rows, hend = half_begin[half] + a.h;
-    const int64_t hi = end < hend ? end : hend;
-    if (lo >= hi) continue;
-    a.rows = rows + (size_t)(lo - first_row) * row_doubles;
-    a.nr = hi - lo; a.m0 = lo - half_begin[half]; a.half = half;
+    phf_half_segment seg;
+    if (!phf_half_cut(total_rows, first_row, num_rows, half, &seg)) continue;
+    a.rows = rows + (size_t)seg.offset * row_doubles;
+    a.nr = seg.nr; a.m0 = seg.m0; a.half = half;
     hipLaunchKernelGGL(batch_means_accumulate_kernel, dim3(blocks_for(a.units, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
     if ((rc = phf_check_launch("batch_means_accumulate_kernel")) != PHF_OK) return rc;
   }
@@ -178,12 +162,13 @@ extern "C" int phf_batch_means_accumulate(const double* rows, int64_t num_rows, 
 
 extern "C" int phf_batch_means_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, const double* workspace,
                                       size_t workspace_bytes, double* out, void* stream) {
+  static const char* who = "phf_batch_means_reduce";
   int nl;
-  int rc = check_shape("phf_batch_means_reduce", num_problems, num_columns, num_chains, total_rows, &nl);
+  int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows, &nl);
   if (rc != PHF_OK) return rc;
   if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_reduce: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains, nl))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_batch_means_reduce: workspace smaller than phf_batch_means_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "batch_means", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_columns, num_chains, nl))) != PHF_OK)
+    return rc;
   BmArgs a = {};
   a.Q = num_problems; a.C = num_chains; a.cols = num_columns; a.nl = nl; a.h = total_rows / 2;
   a.ws = const_cast<double*>(workspace); a.out = out;

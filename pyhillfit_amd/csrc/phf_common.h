@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdarg>
 #include <cstdio>
 
 #include "../../include/pyhillfit_amd.h"
@@ -17,11 +18,19 @@ inline int phf_fail(int code, const char* msg) {
   return code;
 }
 
+// printf-style phf_fail (no argument may point into the error buffer itself)
+__attribute__((format(printf, 2, 3))) inline int phf_failf(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(phf_error_buffer(), kPhfErrorBufferSize, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
 inline int phf_check_launch(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return PHF_OK;
-  std::snprintf(phf_error_buffer(), kPhfErrorBufferSize, "%s: %s", what, hipGetErrorString(e));
-  return PHF_ERR_HIP;
+  return phf_failf(PHF_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
 // The kernels advance moments with hardware fp64 atomics (global_atomic_add_f64 without return) and hand blocks of a queued launch
@@ -63,10 +72,9 @@ inline int phf_require_device_memory(const void* p, const char* what) {
   }
   const bool fine_grained = (attr.allocationFlags & hipDeviceMallocFinegrained) != 0;
   if (attr.type != hipMemoryTypeDevice || attr.isManaged || fine_grained) {
-    std::snprintf(phf_error_buffer(), kPhfErrorBufferSize,
-                  "%s: must be ordinary coarse-grained device memory (hipMalloc), not host-pinned, managed or fine-grained memory: "
-                  "fp64 atomics and release/acquire hand-overs are not guaranteed there", what);
-    return PHF_ERR_INVALID_ARGUMENT;
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT,
+                     "%s: must be ordinary coarse-grained device memory (hipMalloc), not host-pinned, managed or fine-grained memory: "
+                     "fp64 atomics and release/acquire hand-overs are not guaranteed there", what);
   }
   c.ptr[c.next] = p;
   c.dev[c.next] = dev;

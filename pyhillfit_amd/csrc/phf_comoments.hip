@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_comoments.h"
 #include "phf_device_util.h"
 
@@ -183,27 +183,16 @@ int tile_edge(int d) { return d <= kSmallTile ? kSmallTile : kTile; }
 
 // shared argument checks of the four entries
 int check_shape(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || num_columns < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems, num_columns and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (num_columns > kMaxColumns) {
-    std::snprintf(msg, sizeof msg, "%s: at most %d columns (got %d)", who, kMaxColumns, num_columns);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 2 * PHF_CM_MIN_HALF) {
-    std::snprintf(msg, sizeof msg, "%s: a half-chain needs h = floor(total_rows / 2) >= 4 rows (total_rows = %lld)", who, (long long)total_rows);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  int rc = phf_check_positive(who, "num_problems, num_columns and num_chains", {num_problems, num_columns, num_chains});
+  if (rc != PHF_OK) return rc;
+  if (num_columns > kMaxColumns) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: at most %d columns (got %d)", who, kMaxColumns, num_columns);
+  if (total_rows < 2 * PHF_CM_MIN_HALF)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: a half-chain needs h = floor(total_rows / 2) >= 4 rows (total_rows = %lld)", who,
+                     (long long)total_rows);
   const int nb = (num_columns + tile_edge(num_columns) - 1) / tile_edge(num_columns);
   const double tiles = (double)num_problems * ((num_chains + 63) / 64) * (nb * (nb + 1) / 2);
   const double reduce_units = (double)num_problems * (PHF_CM_PAIRS(num_columns) + num_columns);
-  if (tiles / kWaves > 2147483647.0 || reduce_units / kWaves > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
+  return phf_check_grid(who, {tiles / kWaves, reduce_units / kWaves});
 }
 
 size_t workspace_bytes_of(int num_problems, int num_columns, int num_chains) {
@@ -219,28 +208,24 @@ extern "C" size_t phf_comoments_workspace_bytes(int num_problems, int num_column
 
 extern "C" int phf_comoments_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, double* workspace,
                                   size_t workspace_bytes, void* stream) {
-  int rc = check_shape("phf_comoments_init", num_problems, num_columns, num_chains, total_rows);
+  static const char* who = "phf_comoments_init";
+  const int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_init: null workspace");
   const size_t need = workspace_bytes_of(num_problems, num_columns, num_chains);
-  if (workspace_bytes < need) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_init: workspace smaller than phf_comoments_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_comoments_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch("phf_comoments_init");
-  return PHF_OK;
+  return phf_init_workspace(who, "comoments", workspace, workspace_bytes, need, need, stream);
 }
 
 extern "C" int phf_comoments_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
                                         int num_columns, int64_t first_row, int64_t total_rows, double* workspace, size_t workspace_bytes,
                                         void* stream) {
-  int rc = check_shape("phf_comoments_accumulate", num_problems, num_columns, num_chains, total_rows);
+  static const char* who = "phf_comoments_accumulate";
+  int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
-  if (row_stride_cols < num_columns)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_accumulate: row_stride_cols must be >= num_columns");
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
+  if ((rc = phf_check_row_stride(who, row_stride_cols, num_columns, "must be >= num_columns")) != PHF_OK) return rc;
   if (!rows || !workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_accumulate: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_accumulate: workspace smaller than phf_comoments_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "comoments", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_columns, num_chains))) != PHF_OK)
+    return rc;
   if (num_rows == 0) return PHF_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   CmArgs a = {};
@@ -249,14 +234,11 @@ extern "C" int phf_comoments_accumulate(const double* rows, int64_t num_rows, in
   a.ncg = (num_chains + 63) / 64; a.nb = (num_columns + T - 1) / T; a.ntile = a.nb * (a.nb + 1) / 2;
   a.units = (int64_t)num_problems * a.ncg * a.ntile;
   const size_t row_doubles = (size_t)num_problems * row_stride_cols * num_chains;
-  const int64_t half_begin[2] = {0, total_rows - a.h};
   for (int half = 0; half < 2; ++half) {
-    const int64_t lo = first_row > half_begin[half] ? first_row : half_begin[half];
-    const int64_t end = first_row + num_rows, hend = half_begin[half] + a.h;
-    const int64_t hi = end < hend ? end : hend;
-    if (lo >= hi) continue;
-    a.rows = rows + (size_t)(lo - first_row) * row_doubles;
-    a.nr = hi - lo; a.m0 = lo - half_begin[half]; a.half = half;
+    phf_half_segment seg;
+    if (!phf_half_cut(total_rows, first_row, num_rows, half, &seg)) continue;
+    a.rows = rows + (size_t)seg.offset * row_doubles;
+    a.nr = seg.nr; a.m0 = seg.m0; a.half = half;
     if (T == kSmallTile) hipLaunchKernelGGL(cm_accumulate_kernel<kSmallTile>, dim3(blocks_for(a.units, kWaves)), dim3(kThreads), 0, s, a);
     else hipLaunchKernelGGL(cm_accumulate_kernel<kTile>, dim3(blocks_for(a.units, kWaves)), dim3(kThreads), 0, s, a);
     if ((rc = phf_check_launch("cm_accumulate_kernel")) != PHF_OK) return rc;
@@ -266,11 +248,12 @@ extern "C" int phf_comoments_accumulate(const double* rows, int64_t num_rows, in
 
 extern "C" int phf_comoments_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, const double* workspace,
                                     size_t workspace_bytes, double* out, void* stream) {
-  int rc = check_shape("phf_comoments_reduce", num_problems, num_columns, num_chains, total_rows);
+  static const char* who = "phf_comoments_reduce";
+  int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
   if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_reduce: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_comoments_reduce: workspace smaller than phf_comoments_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "comoments", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_columns, num_chains))) != PHF_OK)
+    return rc;
   CmArgs a = {};
   a.Q = num_problems; a.C = num_chains; a.d = num_columns; a.ws = const_cast<double*>(workspace); a.out = out; a.h = total_rows / 2;
   a.units = (int64_t)num_problems * (PHF_CM_PAIRS(num_columns) + num_columns);

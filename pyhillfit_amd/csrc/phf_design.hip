@@ -110,35 +110,24 @@ extern "C" int phf_design_accumulate(int model, int bins, const double* rows, in
                                      int num_chains, int64_t first_row, int every, const double* ln_doses, int num_doses, int num_slots,
                                      double* accumulators, size_t accumulator_bytes, void* stream) {
   static const char* who = "phf_design_accumulate";
-  char msg[kPhfErrorBufferSize];
-  if (model != 1 && model != 2) {
-    std::snprintf(msg, sizeof msg, "%s: model must be 1 or 2 (single-level), got %d", who, model);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (!phf_ds_bins_ok(bins)) {
-    std::snprintf(msg, sizeof msg, "%s: bins must be 128, 256, 512 or 1024 (got %d)", who, bins);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (model != 1 && model != 2)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: model must be 1 or 2 (single-level), got %d", who, model);
+  if (!phf_ds_bins_ok(bins))
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: bins must be 128, 256, 512 or 1024 (got %d)", who, bins);
   if (num_doses < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_design_accumulate: num_doses must be >= 1");
   if (every < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_design_accumulate: every must be >= 1");
   if (num_chains < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_design_accumulate: num_chains must be positive");
   if (num_problems < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_design_accumulate: num_problems must be positive");
-  if (!phf_ds_slots_ok(num_slots)) {
-    std::snprintf(msg, sizeof msg, "%s: num_slots must be even and in 2..%d (got %d)", who, PHF_DS_MAX_SLOTS, num_slots);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (row_stride_cols < model + 1) {
-    std::snprintf(msg, sizeof msg, "%s: row_stride_cols is smaller than the %d parameter columns of model %d", who, model + 1, model);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (!phf_ds_slots_ok(num_slots))
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_slots must be even and in 2..%d (got %d)", who, PHF_DS_MAX_SLOTS, num_slots);
+  if (row_stride_cols < model + 1)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: row_stride_cols is smaller than the %d parameter columns of model %d", who, model + 1, model);
   if (num_rows < 0 || first_row < 0) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_design_accumulate: num_rows and first_row must be >= 0");
   const int64_t units = (int64_t)num_problems * num_doses * num_slots;
   if (units > 2147483647ll - kWaves) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_design_accumulate: too many (problem, dose, slot) units");
-  if (accumulator_bytes < (size_t)units * PHF_DS_ACC_DOUBLES(bins) * sizeof(double)) {
-    std::snprintf(msg, sizeof msg, "%s: the accumulators are smaller than num_problems x num_doses x num_slots x %d doubles", who,
-                  PHF_DS_ACC_DOUBLES(bins));
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (accumulator_bytes < (size_t)units * PHF_DS_ACC_DOUBLES(bins) * sizeof(double))
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: the accumulators are smaller than num_problems x num_doses x num_slots x %d doubles", who,
+                     PHF_DS_ACC_DOUBLES(bins));
   const int64_t used = phf_ds_rows_used(first_row, num_rows, every);
   if (used == 0) return PHF_OK;                                          // no row of the call is used: no launch
   if (!rows || !ln_doses || !accumulators) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_design_accumulate: null pointer");

@@ -25,7 +25,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_half_chains.h"
+#include "phf_host_checks.h"
 #include "phf_device_util.h"
 
 #define PHF_DIAG_UNROLL _Pragma("unroll")
@@ -209,26 +210,15 @@ __global__ __launch_bounds__(kThreads) void diag_reduce_kernel(const DiagArgs a)
 
 // shared argument checks of the four entries; on success fills the layout
 int check_shape(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags, Layout* lay) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || num_columns < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems, num_columns and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (lags < 1) {
-    std::snprintf(msg, sizeof msg, "%s: the lag limit K must be positive (got %d)", who, lags);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 8) {
-    std::snprintf(msg, sizeof msg, "%s: a half-chain needs h = floor(total_rows / 2) >= 4 rows (total_rows = %lld)", who, (long long)total_rows);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  int rc = phf_check_positive(who, "num_problems, num_columns and num_chains", {num_problems, num_columns, num_chains});
+  if (rc != PHF_OK) return rc;
+  if (lags < 1) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: the lag limit K must be positive (got %d)", who, lags);
+  if (total_rows < 8)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: a half-chain needs h = floor(total_rows / 2) >= 4 rows (total_rows = %lld)", who,
+                     (long long)total_rows);
   *lay = layout_of(lags, total_rows);
   const double units = (double)num_problems * num_columns * ((num_chains + 63) / 64) * ((lay->L + kLagBlock - 1) / kLagBlock);
-  if (units / kWaves > 2147483647.0 || (double)num_problems * num_columns * num_chains / kThreads > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
+  return phf_check_grid(who, {units / kWaves, (double)num_problems * num_columns * num_chains / kThreads});
 }
 
 size_t workspace_bytes_of(int num_problems, int num_columns, int num_chains, const Layout& lay) {
@@ -250,15 +240,12 @@ extern "C" int phf_diagnostics_effective_lags(int64_t total_rows, int lags) {
 
 extern "C" int phf_diagnostics_init(int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags, double* workspace,
                                     size_t workspace_bytes, void* stream) {
+  static const char* who = "phf_diagnostics_init";
   Layout lay;
-  int rc = check_shape("phf_diagnostics_init", num_problems, num_columns, num_chains, total_rows, lags, &lay);
+  const int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows, lags, &lay);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_init: null workspace");
   const size_t need = workspace_bytes_of(num_problems, num_columns, num_chains, lay);
-  if (workspace_bytes < need) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_init: workspace smaller than phf_diagnostics_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_diagnostics_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch("phf_diagnostics_init");
-  return PHF_OK;
+  return phf_init_workspace(who, "diagnostics", workspace, workspace_bytes, need, need, stream);
 }
 
 extern "C" int phf_diagnostics_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
@@ -268,13 +255,11 @@ extern "C" int phf_diagnostics_accumulate(const double* rows, int64_t num_rows, 
   Layout lay;
   int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows, lags, &lay);
   if (rc != PHF_OK) return rc;
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
-  if (row_stride_cols < num_columns)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_accumulate: row_stride_cols must be >= num_columns");
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
+  if ((rc = phf_check_row_stride(who, row_stride_cols, num_columns, "must be >= num_columns")) != PHF_OK) return rc;
   if (!rows || !workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_accumulate: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains, lay))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_accumulate: workspace smaller than phf_diagnostics_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "diagnostics", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_columns, num_chains, lay))) != PHF_OK)
+    return rc;
   if (num_rows == 0) return PHF_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DiagArgs a = {};
@@ -282,21 +267,18 @@ extern "C" int phf_diagnostics_accumulate(const double* rows, int64_t num_rows, 
   a.ncg = (num_chains + 63) / 64; a.nlb = (lay.L + kLagBlock - 1) / kLagBlock;
   const size_t row_doubles = (size_t)num_problems * row_stride_cols * num_chains;
   const int64_t per_chain = (int64_t)num_problems * num_columns * num_chains;
-  const int64_t half_begin[2] = {0, total_rows - lay.h};
   for (int half = 0; half < 2; ++half) {
-    const int64_t lo = first_row > half_begin[half] ? first_row : half_begin[half];
-    const int64_t end = first_row + num_rows, hend = half_begin[half] + lay.h;
-    const int64_t hi = end < hend ? end : hend;
-    if (lo >= hi) continue;
-    a.rows = rows + (size_t)(lo - first_row) * row_doubles;
-    a.nr = hi - lo; a.m0 = lo - half_begin[half]; a.half = half;
+    phf_half_segment seg;
+    if (!phf_half_cut(total_rows, first_row, num_rows, half, &seg)) continue;
+    a.rows = rows + (size_t)seg.offset * row_doubles;
+    a.nr = seg.nr; a.m0 = seg.m0; a.half = half;
     a.units = (int64_t)num_problems * num_columns * a.ncg * a.nlb;
     hipLaunchKernelGGL(diag_lag_kernel, dim3(blocks_for(a.units, kWaves)), dim3(kThreads), 0, s, a);
     if ((rc = phf_check_launch("diag_lag_kernel")) != PHF_OK) return rc;
     a.units = per_chain;
     hipLaunchKernelGGL(diag_update_kernel, dim3(blocks_for(a.units, kThreads)), dim3(kThreads), 0, s, a);
     if ((rc = phf_check_launch("diag_update_kernel")) != PHF_OK) return rc;
-    if (hi == hend) {
+    if (seg.closes) {
       hipLaunchKernelGGL(diag_close_kernel, dim3(blocks_for(a.units, kThreads)), dim3(kThreads), 0, s, a);
       if ((rc = phf_check_launch("diag_close_kernel")) != PHF_OK) return rc;
     }
@@ -306,12 +288,13 @@ extern "C" int phf_diagnostics_accumulate(const double* rows, int64_t num_rows, 
 
 extern "C" int phf_diagnostics_reduce(int num_problems, int num_columns, int num_chains, int64_t total_rows, int lags,
                                       const double* workspace, size_t workspace_bytes, double* out, void* stream) {
+  static const char* who = "phf_diagnostics_reduce";
   Layout lay;
-  int rc = check_shape("phf_diagnostics_reduce", num_problems, num_columns, num_chains, total_rows, lags, &lay);
+  int rc = check_shape(who, num_problems, num_columns, num_chains, total_rows, lags, &lay);
   if (rc != PHF_OK) return rc;
   if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_reduce: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_columns, num_chains, lay))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_diagnostics_reduce: workspace smaller than phf_diagnostics_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "diagnostics", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_columns, num_chains, lay))) != PHF_OK)
+    return rc;
   DiagArgs a = {};
   a.Q = num_problems; a.C = num_chains; a.cols = num_columns; a.lay = lay; a.ws = const_cast<double*>(workspace); a.out = out;
   a.units = (int64_t)num_problems * num_columns * (lay.L + 2);

@@ -189,9 +189,7 @@ inline phf_grid_split phf_grid_split_of(unsigned n, int slots) {
 // bins: a power of two in [kGridMinBins, max_bins] (the caller's bin kernel sets max_bins by its LDS per bin)
 inline int phf_grid_check_bins(const char* who, int bins, int max_bins) {
   if (bins >= kGridMinBins && bins <= max_bins && (bins & (bins - 1)) == 0) return PHF_OK;
-  char msg[kPhfErrorBufferSize];
-  std::snprintf(msg, sizeof msg, "%s: bins must be a power of two in [%d, %d] (got %d)", who, kGridMinBins, max_bins, bins);
-  return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+  return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: bins must be a power of two in [%d, %d] (got %d)", who, kGridMinBins, max_bins, bins);
 }
 #endif /* __HIPCC__ */
 

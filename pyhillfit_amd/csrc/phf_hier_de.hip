@@ -97,15 +97,10 @@ __global__ __launch_bounds__(kThreads) void de_stats_kernel(int Q, int ncg, cons
 }
 
 int check_shape(const char* who, int num_problems, int num_chains) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if ((double)num_problems * num_chains > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems * num_chains must fit in an int32", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (num_problems < 1 || num_chains < 1)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_problems and num_chains must be positive", who);
+  if ((double)num_problems * num_chains > 2147483647.0)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_problems * num_chains must fit in an int32", who);
   return PHF_OK;
 }
 

@@ -134,31 +134,18 @@ __global__ __launch_bounds__(kThreads) void gap_max_kernel(const double* g, int6
 size_t lds_bytes(int nq, int stride) { return ((size_t)3 * nq + (size_t)kWaves * 2 * stride) * sizeof(double); }
 
 int check_common(const char* who, const phf_pointwise_points* pts, int num_expts, const double* nodes, int num_nodes) {
-  char msg[kPhfErrorBufferSize];
-  if (!pts || !pts->ln_conc || !pts->response || !pts->tag || !pts->count) {
-    std::snprintf(msg, sizeof msg, "%s: null points", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (pts->stride < 1 || pts->num_problems < 1) {
-    std::snprintf(msg, sizeof msg, "%s: the points must have stride >= 1 and at least one problem", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (pts->stride > kMaxStride) {
-    std::snprintf(msg, sizeof msg, "%s: at most %d points per problem (stride %d)", who, kMaxStride, pts->stride);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (num_expts < 1 || num_expts > kMaxExpts) {
-    std::snprintf(msg, sizeof msg, "%s: num_expts must be in 1..%d (got %d)", who, kMaxExpts, num_expts);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (!phf_mg_nodes_ok(num_nodes)) {
-    std::snprintf(msg, sizeof msg, "%s: num_nodes must be 32, 64, 128 or 256 (got %d)", who, num_nodes);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (!nodes) {
-    std::snprintf(msg, sizeof msg, "%s: null nodes", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (!pts || !pts->ln_conc || !pts->response || !pts->tag || !pts->count)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: null points", who);
+  if (pts->stride < 1 || pts->num_problems < 1)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: the points must have stride >= 1 and at least one problem", who);
+  if (pts->stride > kMaxStride)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: at most %d points per problem (stride %d)", who, kMaxStride, pts->stride);
+  if (num_expts < 1 || num_expts > kMaxExpts)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_expts must be in 1..%d (got %d)", who, kMaxExpts, num_expts);
+  if (!phf_mg_nodes_ok(num_nodes))
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_nodes must be 32, 64, 128 or 256 (got %d)", who, num_nodes);
+  if (!nodes)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: null nodes", who);
   return PHF_OK;
 }
 
@@ -166,9 +153,7 @@ template <bool ROWS>
 int launch(const char* who, const MgArgs& a, hipStream_t stream) {
   const int64_t blocks = (a.units + kWaves - 1) / kWaves;
   if (blocks > 2147483647ll) {
-    char msg[kPhfErrorBufferSize];
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer draws per call)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: launch grid too large (fewer draws per call)", who);
   }
   hipLaunchKernelGGL(marginal_kernel<ROWS>, dim3((unsigned)blocks), dim3(kThreads), lds_bytes(a.nq, a.pts.stride), stream, a);
   return phf_check_launch(who);

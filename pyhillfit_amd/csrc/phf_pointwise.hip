@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_point_block.h"
 
 namespace {
@@ -187,39 +187,15 @@ __global__ __launch_bounds__(kThreads) void waic_reduce_kernel(const WaicArgs a)
 }
 
 int check_shape(const char* who, int num_problems, int stride, int num_chains, int64_t total_rows) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || stride < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems, stride and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 1) {
-    std::snprintf(msg, sizeof msg, "%s: total_rows must be positive (got %lld)", who, (long long)total_rows);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  const int rc = phf_check_positive(who, "num_problems, stride and num_chains", {num_problems, stride, num_chains});
+  if (rc != PHF_OK) return rc;
+  if (total_rows < 1) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: total_rows must be positive (got %lld)", who, (long long)total_rows);
   const double units = (double)num_problems * ((num_chains + 63) / 64) * ((stride + kPtBlock - 1) / kPtBlock);
-  if (units > 2147483647.0 || (double)num_problems * stride > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
+  return phf_check_grid(who, {units, (double)num_problems * stride});
 }
 
 size_t workspace_bytes_of(int num_problems, int stride, int num_chains) {
   return (size_t)num_problems * stride * kFields * (size_t)num_chains * sizeof(double);
-}
-
-int check_points(const char* who, const phf_pointwise_points* pts, int num_problems) {
-  char msg[kPhfErrorBufferSize];
-  if (!pts || !pts->ln_conc || !pts->response || !pts->tag || !pts->count) {
-    std::snprintf(msg, sizeof msg, "%s: null points", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (pts->stride < 1 || pts->num_problems < 1 || (num_problems > 0 && pts->num_problems != num_problems)) {
-    std::snprintf(msg, sizeof msg, "%s: the points must have stride >= 1 and one row per problem (%d rows, %d problems)", who,
-                  pts->num_problems, num_problems);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
 }
 
 }  // namespace
@@ -227,7 +203,7 @@ int check_points(const char* who, const phf_pointwise_points* pts, int num_probl
 extern "C" int phf_pointwise_loglik_single_level(const phf_pointwise_points* pts, int model, int64_t m, const int32_t* problem_index,
                                                  const double* theta, double* out, void* stream) {
   static const char* who = "phf_pointwise_loglik_single_level";
-  int rc = check_points(who, pts, 0);
+  int rc = phf_check_points(who, pts, 0, 0);
   if (rc != PHF_OK) return rc;
   if (model != 1 && model != 2) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_pointwise_loglik_single_level: model must be 1 or 2");
   if (m < 0 || (m > 0 && (!problem_index || !theta || !out)))
@@ -242,7 +218,7 @@ extern "C" int phf_pointwise_loglik_single_level(const phf_pointwise_points* pts
 extern "C" int phf_pointwise_loglik_hierarchical(const phf_pointwise_points* pts, int num_expts, int64_t m, const int32_t* problem_index,
                                                  const double* theta, double* out, void* stream) {
   static const char* who = "phf_pointwise_loglik_hierarchical";
-  int rc = check_points(who, pts, 0);
+  int rc = phf_check_points(who, pts, 0, 0);
   if (rc != PHF_OK) return rc;
   if (num_expts < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_pointwise_loglik_hierarchical: num_expts must be positive");
   if (m < 0 || (m > 0 && (!problem_index || !theta || !out)))
@@ -260,14 +236,11 @@ extern "C" size_t phf_waic_workspace_bytes(int num_problems, int stride, int num
 
 extern "C" int phf_waic_init(int num_problems, int stride, int num_chains, int64_t total_rows, double* workspace, size_t workspace_bytes,
                              void* stream) {
-  int rc = check_shape("phf_waic_init", num_problems, stride, num_chains, total_rows);
+  static const char* who = "phf_waic_init";
+  const int rc = check_shape(who, num_problems, stride, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_init: null workspace");
   const size_t need = workspace_bytes_of(num_problems, stride, num_chains);
-  if (workspace_bytes < need) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_init: workspace smaller than phf_waic_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_waic_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch("phf_waic_init");
-  return PHF_OK;
+  return phf_init_workspace(who, "waic", workspace, workspace_bytes, need, need, stream);
 }
 
 namespace {
@@ -276,33 +249,16 @@ namespace {
 int waic_accumulate(const char* who, const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
                     int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, double* workspace,
                     size_t workspace_bytes, void* stream) {
-  char msg[kPhfErrorBufferSize];
-  int rc = check_points(who, pts, num_problems);
+  int rc = phf_check_points(who, pts, num_problems, 0);
   if (rc != PHF_OK) return rc;
   if ((rc = check_shape(who, num_problems, pts->stride, num_chains, total_rows)) != PHF_OK) return rc;
-  if (likelihood != kGiven) {                                      // phf_waic_accumulate's own codes
-    if (likelihood < 1 || likelihood > kHierarchical)
-      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: likelihood must be 1, 2 (single-level model) or 3 (hierarchical)");
-    if (likelihood == kHierarchical && num_expts < 1)
-      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_accumulate: the hierarchical likelihood needs num_expts >= 1");
-  }
+  if (likelihood != kGiven && (rc = phf_check_likelihood(who, likelihood, num_expts)) != PHF_OK) return rc;   // phf_waic_accumulate's own codes
   const int cols = likelihood == kGiven ? pts->stride : likelihood == kHierarchical ? 5 + 2 * num_expts : likelihood + 1;
-  if (row_stride_cols < cols) {
-    std::snprintf(msg, sizeof msg, "%s: row_stride_cols is smaller than the columns the likelihood reads", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows) {
-    std::snprintf(msg, sizeof msg, "%s: rows [first_row, first_row + num_rows) must lie in [0, total_rows)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (!rows || !workspace) {
-    std::snprintf(msg, sizeof msg, "%s: null pointer", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (workspace_bytes < workspace_bytes_of(num_problems, pts->stride, num_chains)) {
-    std::snprintf(msg, sizeof msg, "%s: workspace smaller than phf_waic_workspace_bytes()", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if ((rc = phf_check_row_stride(who, row_stride_cols, cols, "is smaller than the columns the likelihood reads")) != PHF_OK) return rc;
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
+  if (!rows || !workspace) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+  if ((rc = phf_check_workspace(who, "waic", workspace, workspace_bytes, workspace_bytes_of(num_problems, pts->stride, num_chains))) != PHF_OK)
+    return rc;
   if (num_rows == 0) return PHF_OK;
   WaicArgs a = {};
   a.pts = *pts; a.rows = rows; a.nr = num_rows; a.first_row = first_row; a.total_rows = total_rows;
@@ -337,11 +293,11 @@ extern "C" int phf_waic_accumulate_given(const phf_pointwise_points* pts, const 
 
 extern "C" int phf_waic_reduce(int num_problems, int stride, int num_chains, int64_t total_rows, const double* workspace,
                                size_t workspace_bytes, double* out, void* stream) {
-  int rc = check_shape("phf_waic_reduce", num_problems, stride, num_chains, total_rows);
+  static const char* who = "phf_waic_reduce";
+  int rc = check_shape(who, num_problems, stride, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
   if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_reduce: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, stride, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_waic_reduce: workspace smaller than phf_waic_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "waic", workspace, workspace_bytes, workspace_bytes_of(num_problems, stride, num_chains))) != PHF_OK) return rc;
   WaicArgs a = {};
   a.pts.stride = stride; a.Q = num_problems; a.C = num_chains; a.total_rows = total_rows; a.ws = const_cast<double*>(workspace);
   a.out = out;

@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_point_block.h"
 #include "phf_ppc.h"
 
@@ -283,60 +283,16 @@ __global__ __launch_bounds__(kThreads) void ppc_replicate_kernel(const phf_point
 }
 
 int check_shape(const char* who, int num_problems, int stride, int num_chains, int64_t total_rows) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || stride < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems, stride and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (stride > kMaxStride) {
-    std::snprintf(msg, sizeof msg, "%s: at most %d points per problem (stride %d)", who, kMaxStride, stride);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 1) {
-    std::snprintf(msg, sizeof msg, "%s: total_rows must be positive (got %lld)", who, (long long)total_rows);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  const int rc = phf_check_positive(who, "num_problems, stride and num_chains", {num_problems, stride, num_chains});
+  if (rc != PHF_OK) return rc;
+  if (stride > kMaxStride) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: at most %d points per problem (stride %d)", who, kMaxStride, stride);
+  if (total_rows < 1) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: total_rows must be positive (got %lld)", who, (long long)total_rows);
   const double units = (double)num_problems * ((num_chains + 63) / 64) * ((stride + kPtBlock - 1) / kPtBlock);
-  if (units > 2147483647.0 || (double)num_problems * (kHead + stride) > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
+  return phf_check_grid(who, {units, (double)num_problems * (kHead + stride)});
 }
 
 size_t workspace_bytes_of(int num_problems, int stride, int num_chains) {
   return (size_t)num_problems * (kHead + (size_t)stride) * (size_t)num_chains * sizeof(double);
-}
-
-int check_points(const char* who, const phf_pointwise_points* pts, int num_problems) {
-  char msg[kPhfErrorBufferSize];
-  if (!pts || !pts->ln_conc || !pts->response || !pts->tag || !pts->count) {
-    std::snprintf(msg, sizeof msg, "%s: null points", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (pts->stride < 1 || pts->num_problems < 1 || (num_problems > 0 && pts->num_problems != num_problems)) {
-    std::snprintf(msg, sizeof msg, "%s: the points must have stride >= 1 and one row per problem (%d rows, %d problems)", who,
-                  pts->num_problems, num_problems);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (pts->stride > kMaxStride) {
-    std::snprintf(msg, sizeof msg, "%s: at most %d points per problem (stride %d)", who, kMaxStride, pts->stride);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
-}
-
-int check_likelihood(const char* who, int likelihood, int num_expts) {
-  char msg[kPhfErrorBufferSize];
-  if (likelihood < 1 || likelihood > kHierarchical) {
-    std::snprintf(msg, sizeof msg, "%s: likelihood must be 1, 2 (single-level model) or 3 (hierarchical)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (likelihood == kHierarchical && num_expts < 1) {
-    std::snprintf(msg, sizeof msg, "%s: the hierarchical likelihood needs num_expts >= 1", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
 }
 
 }  // namespace
@@ -348,14 +304,11 @@ extern "C" size_t phf_ppc_workspace_bytes(int num_problems, int stride, int num_
 
 extern "C" int phf_ppc_init(int num_problems, int stride, int num_chains, int64_t total_rows, double* workspace, size_t workspace_bytes,
                             void* stream) {
-  int rc = check_shape("phf_ppc_init", num_problems, stride, num_chains, total_rows);
+  static const char* who = "phf_ppc_init";
+  const int rc = check_shape(who, num_problems, stride, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_init: null workspace");
   const size_t need = workspace_bytes_of(num_problems, stride, num_chains);
-  if (workspace_bytes < need) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_init: workspace smaller than phf_ppc_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_ppc_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch("phf_ppc_init");
-  return PHF_OK;
+  return phf_init_workspace(who, "ppc", workspace, workspace_bytes, need, need, stream);
 }
 
 extern "C" int phf_ppc_accumulate(const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
@@ -363,20 +316,18 @@ extern "C" int phf_ppc_accumulate(const phf_pointwise_points* pts, int likelihoo
                                   const uint32_t* problem_id, uint32_t chain_id_base, uint64_t seed, double* workspace,
                                   size_t workspace_bytes, void* stream) {
   static const char* who = "phf_ppc_accumulate";
-  int rc = check_points(who, pts, num_problems);
+  int rc = phf_check_points(who, pts, num_problems, kMaxStride);
   if (rc != PHF_OK) return rc;
   if ((rc = check_shape(who, num_problems, pts->stride, num_chains, total_rows)) != PHF_OK) return rc;
-  if ((rc = check_likelihood(who, likelihood, num_expts)) != PHF_OK) return rc;
+  if ((rc = phf_check_likelihood(who, likelihood, num_expts)) != PHF_OK) return rc;
   const int cols = likelihood == kHierarchical ? 5 + 2 * num_expts : likelihood + 1;
-  if (row_stride_cols < cols)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_accumulate: row_stride_cols is smaller than the columns the likelihood reads");
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
+  if ((rc = phf_check_row_stride(who, row_stride_cols, cols, "is smaller than the columns the likelihood reads")) != PHF_OK) return rc;
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
   if (total_rows > 4294967296LL)
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_accumulate: total_rows must fit the 32-bit row word of the random stream");
   if (!rows || !workspace || !problem_id) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_accumulate: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, pts->stride, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_accumulate: workspace smaller than phf_ppc_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "ppc", workspace, workspace_bytes, workspace_bytes_of(num_problems, pts->stride, num_chains))) != PHF_OK)
+    return rc;
   if (num_rows == 0) return PHF_OK;
   PpcArgs a = {};
   a.pts = *pts; a.rows = rows; a.nr = num_rows; a.first_row = first_row; a.total_rows = total_rows;
@@ -403,11 +354,11 @@ extern "C" int phf_ppc_accumulate(const phf_pointwise_points* pts, int likelihoo
 
 extern "C" int phf_ppc_reduce(int num_problems, int stride, int num_chains, int64_t total_rows, const double* workspace,
                               size_t workspace_bytes, double* out, void* stream) {
-  int rc = check_shape("phf_ppc_reduce", num_problems, stride, num_chains, total_rows);
+  static const char* who = "phf_ppc_reduce";
+  int rc = check_shape(who, num_problems, stride, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
   if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_reduce: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, stride, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_reduce: workspace smaller than phf_ppc_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "ppc", workspace, workspace_bytes, workspace_bytes_of(num_problems, stride, num_chains))) != PHF_OK) return rc;
   const int64_t units = (int64_t)num_problems * (kHead + stride);
   hipLaunchKernelGGL(ppc_reduce_kernel, dim3(blocks_for(units, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), workspace,
                      units, num_chains, out);
@@ -418,9 +369,9 @@ extern "C" int phf_ppc_replicate(const phf_pointwise_points* pts, int likelihood
                                  const double* theta, const uint32_t* counter, uint64_t seed, double* y_rep, double* stats,
                                  void* stream) {
   static const char* who = "phf_ppc_replicate";
-  int rc = check_points(who, pts, 0);
+  int rc = phf_check_points(who, pts, 0, kMaxStride);
   if (rc != PHF_OK) return rc;
-  if ((rc = check_likelihood(who, likelihood, num_expts)) != PHF_OK) return rc;
+  if ((rc = phf_check_likelihood(who, likelihood, num_expts)) != PHF_OK) return rc;
   if (m < 0 || (m > 0 && (!problem_index || !theta || !counter || !y_rep || !stats)))
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_ppc_replicate: m must be >= 0 and the arrays non-null");
   if (m == 0) return PHF_OK;

@@ -42,7 +42,7 @@
 #include <cstdint>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_point_block.h"
 
 namespace {
@@ -559,31 +559,18 @@ int64_t next_threshold_row(int64_t r) {
 
 // validate a shape and lay out its workspace; PHF_OK or PHF_ERR_INVALID_ARGUMENT with the reason
 int layout_of(const char* who, int num_problems, int stride, int num_chains, int64_t total_rows, int tail_per_chain, Layout* L) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || stride < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems, stride and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 1 || (double)total_rows * num_chains < 2.0) {
-    std::snprintf(msg, sizeof msg, "%s: total_rows must be positive and total_rows x num_chains at least 2 (got %lld x %d)", who,
-                  (long long)total_rows, num_chains);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (tail_per_chain < 0) {
-    std::snprintf(msg, sizeof msg, "%s: tail_per_chain must be >= 0 (0: the default rule)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  int rc = phf_check_positive(who, "num_problems, stride and num_chains", {num_problems, stride, num_chains});
+  if (rc != PHF_OK) return rc;
+  if (total_rows < 1 || (double)total_rows * num_chains < 2.0)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: total_rows must be positive and total_rows x num_chains at least 2 (got %lld x %d)", who,
+                     (long long)total_rows, num_chains);
+  if (tail_per_chain < 0) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: tail_per_chain must be >= 0 (0: the default rule)", who);
   const double S = (double)total_rows * num_chains;
-  if (S > 0x1p52) {
-    std::snprintf(msg, sizeof msg, "%s: total_rows x num_chains too large", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (S > 0x1p52) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: total_rows x num_chains too large", who);
   const int64_t M = tail_length_of((int64_t)S);
-  if (M > kMaxTail) {
-    std::snprintf(msg, sizeof msg, "%s: the tail length M = %lld exceeds %lld (fewer draws per point)", who, (long long)M,
-                  (long long)kMaxTail);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (M > kMaxTail)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: the tail length M = %lld exceeds %lld (fewer draws per point)", who, (long long)M,
+                     (long long)kMaxTail);
   const int64_t pts = (int64_t)num_problems * stride;
   const int64_t whole = M + 1 < total_rows ? M + 1 : total_rows;   // a chain never needs more: all of its draws, or the whole tail
   const bool hbm = M + 1 > kLdsTail;
@@ -595,16 +582,11 @@ int layout_of(const char* who, int num_problems, int stride, int num_chains, int
   int64_t k = tail_per_chain == 0 ? dflt : tail_per_chain;
   if (k > whole) k = whole;
   const int64_t held = (k < total_rows ? k : total_rows) * (int64_t)num_chains;
-  if (held < M + 1) {
-    std::snprintf(msg, sizeof msg, "%s: tail_per_chain %lld x %d chains holds fewer than the M + 1 = %lld smallest values", who,
-                  (long long)k, num_chains, (long long)(M + 1));
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (held < M + 1)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: tail_per_chain %lld x %d chains holds fewer than the M + 1 = %lld smallest values", who,
+                     (long long)k, num_chains, (long long)(M + 1));
   const double units = (double)num_problems * ((num_chains + 63) / 64) * ((stride + kPtBlock - 1) / kPtBlock);
-  if (units > 2147483647.0 || (double)num_problems * stride > 2147483647.0 || (double)k * num_chains > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if ((rc = phf_check_grid(who, {units, (double)num_problems * stride, (double)k * num_chains})) != PHF_OK) return rc;
   L->M = M;
   L->k = (int)k;
   L->hbm = hbm;
@@ -614,20 +596,6 @@ int layout_of(const char* who, int num_problems, int stride, int num_chains, int
   L->thr = (size_t)pts;
   L->heap = (size_t)pts * k * num_chains;
   L->scratch = L->hbm ? (size_t)L->groups * 2 * L->p2 : 0;
-  return PHF_OK;
-}
-
-int check_points(const char* who, const phf_pointwise_points* pts, int num_problems) {
-  char msg[kPhfErrorBufferSize];
-  if (!pts || !pts->ln_conc || !pts->response || !pts->tag || !pts->count) {
-    std::snprintf(msg, sizeof msg, "%s: null points", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (pts->stride < 1 || pts->num_problems < 1 || (num_problems > 0 && pts->num_problems != num_problems)) {
-    std::snprintf(msg, sizeof msg, "%s: the points must have stride >= 1 and one row per problem (%d rows, %d problems)", who,
-                  pts->num_problems, num_problems);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
   return PHF_OK;
 }
 
@@ -653,17 +621,14 @@ extern "C" size_t phf_psis_workspace_bytes(int num_problems, int stride, int num
 
 extern "C" int phf_psis_init(int num_problems, int stride, int num_chains, int64_t total_rows, int tail_per_chain, double* workspace,
                              size_t workspace_bytes, void* stream) {
+  static const char* who = "phf_psis_init";
   Layout L;
-  int rc = layout_of("phf_psis_init", num_problems, stride, num_chains, total_rows, tail_per_chain, &L);
+  int rc = layout_of(who, num_problems, stride, num_chains, total_rows, tail_per_chain, &L);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_init: null workspace");
-  if (workspace_bytes < L.bytes()) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_init: workspace smaller than phf_psis_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_psis_init: workspace")) != PHF_OK) return rc;
   // the fields (fill counts) and T = +inf: a heap slot is read only once written
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(workspace, 0, L.fields * sizeof(double), s) != hipSuccess) return phf_check_launch("phf_psis_init");
-  hipLaunchKernelGGL(psis_init_thr_kernel, dim3(blocks_for((int64_t)L.thr, kThreads)), dim3(kThreads), 0, s, workspace + L.fields,
-                     (int64_t)L.thr);
+  if ((rc = phf_init_workspace(who, "psis", workspace, workspace_bytes, L.bytes(), L.fields * sizeof(double), stream)) != PHF_OK) return rc;
+  hipLaunchKernelGGL(psis_init_thr_kernel, dim3(blocks_for((int64_t)L.thr, kThreads)), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     workspace + L.fields, (int64_t)L.thr);
   return phf_check_launch("psis_init_thr_kernel");
 }
 
@@ -673,34 +638,16 @@ namespace {
 int psis_accumulate(const char* who, const phf_pointwise_points* pts, int likelihood, int num_expts, const double* rows, int64_t num_rows,
                     int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int64_t total_rows, int tail_per_chain,
                     double* workspace, size_t workspace_bytes, void* stream) {
-  char msg[kPhfErrorBufferSize];
-  int rc = check_points(who, pts, num_problems);
+  int rc = phf_check_points(who, pts, num_problems, 0);
   if (rc != PHF_OK) return rc;
   Layout L;
   if ((rc = layout_of(who, num_problems, pts->stride, num_chains, total_rows, tail_per_chain, &L)) != PHF_OK) return rc;
-  if (likelihood != kGiven) {                                      // phf_psis_accumulate's own codes
-    if (likelihood < 1 || likelihood > kHierarchical)
-      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: likelihood must be 1, 2 (single-level model) or 3 (hierarchical)");
-    if (likelihood == kHierarchical && num_expts < 1)
-      return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_accumulate: the hierarchical likelihood needs num_expts >= 1");
-  }
+  if (likelihood != kGiven && (rc = phf_check_likelihood(who, likelihood, num_expts)) != PHF_OK) return rc;   // phf_psis_accumulate's own codes
   const int cols = likelihood == kGiven ? pts->stride : likelihood == kHierarchical ? 5 + 2 * num_expts : likelihood + 1;
-  if (row_stride_cols < cols) {
-    std::snprintf(msg, sizeof msg, "%s: row_stride_cols is smaller than the columns the likelihood reads", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows) {
-    std::snprintf(msg, sizeof msg, "%s: rows [first_row, first_row + num_rows) must lie in [0, total_rows)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (!rows || !workspace) {
-    std::snprintf(msg, sizeof msg, "%s: null pointer", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (workspace_bytes < L.bytes()) {
-    std::snprintf(msg, sizeof msg, "%s: workspace smaller than phf_psis_workspace_bytes()", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if ((rc = phf_check_row_stride(who, row_stride_cols, cols, "is smaller than the columns the likelihood reads")) != PHF_OK) return rc;
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
+  if (!rows || !workspace) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: null pointer", who);
+  if ((rc = phf_check_workspace(who, "psis", workspace, workspace_bytes, L.bytes())) != PHF_OK) return rc;
   if (num_rows == 0) return PHF_OK;
   PsisArgs a = {};
   a.pts = *pts; a.rows = rows; a.nr = num_rows; a.first_row = first_row; a.total_rows = total_rows;
@@ -750,13 +697,12 @@ extern "C" int phf_psis_accumulate_given(const phf_pointwise_points* pts, const 
 extern "C" int phf_psis_reduce(const phf_pointwise_points* pts, int num_problems, int num_chains, int64_t total_rows, int tail_per_chain,
                                double* workspace, size_t workspace_bytes, double* out, double* tail_out, void* stream) {
   static const char* who = "phf_psis_reduce";
-  int rc = check_points(who, pts, num_problems);
+  int rc = phf_check_points(who, pts, num_problems, 0);
   if (rc != PHF_OK) return rc;
   Layout L;
   if ((rc = layout_of(who, num_problems, pts->stride, num_chains, total_rows, tail_per_chain, &L)) != PHF_OK) return rc;
   if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_reduce: null pointer");
-  if (workspace_bytes < L.bytes())
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_psis_reduce: workspace smaller than phf_psis_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "psis", workspace, workspace_bytes, L.bytes())) != PHF_OK) return rc;
   PsisArgs a = {};
   a.pts = *pts; a.Q = num_problems; a.C = num_chains; a.total_rows = total_rows;
   a.k = L.k; a.M = (int32_t)L.M; a.p2 = (int32_t)L.p2;

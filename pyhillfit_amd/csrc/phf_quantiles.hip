@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_grid.h"
 #include "phf_hier_bands.h"
 #include "phf_pointwise.h"
@@ -241,55 +241,24 @@ Layout layout_of(int num_problems, int num_columns, int curve_points, int bins) 
 }
 
 int check_geometry(const char* who, int num_problems, int num_columns, int curve_points, int bins) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || num_columns < 0 || curve_points < 0 || num_columns + curve_points < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems must be positive, num_columns and curve_points non-negative, not both 0", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (num_problems < 1 || num_columns < 0 || curve_points < 0 || num_columns + curve_points < 1)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_problems must be positive, num_columns and curve_points non-negative, not both 0", who);
   if (phf_grid_check_bins(who, bins, kMaxBins) != PHF_OK) return PHF_ERR_INVALID_ARGUMENT;
-  if ((double)num_problems * (num_columns + curve_points) > 2147483647.0 / 8) {
-    std::snprintf(msg, sizeof msg, "%s: too many slots (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
-}
-
-int check_workspace(const char* who, const void* ws, size_t bytes, const Layout& l) {
-  char msg[kPhfErrorBufferSize];
-  if (!ws) {
-    std::snprintf(msg, sizeof msg, "%s: null workspace", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (bytes < l.total()) {
-    std::snprintf(msg, sizeof msg, "%s: workspace smaller than phf_quantiles_workspace_bytes()", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if ((double)num_problems * (num_columns + curve_points) > 2147483647.0 / 8)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: too many slots (fewer problems per workspace)", who);
   return PHF_OK;
 }
 
 int check_rows(const char* who, const double* rows, int64_t num_rows, int row_stride_cols, int num_chains, int needed_cols,
                int64_t first_row, int64_t total_rows) {
-  char msg[kPhfErrorBufferSize];
-  if (num_chains < 1 || row_stride_cols < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_chains and row_stride_cols must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (row_stride_cols < needed_cols) {
-    std::snprintf(msg, sizeof msg, "%s: row_stride_cols (%d) is smaller than the columns read (%d)", who, row_stride_cols, needed_cols);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 1 || num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows) {
-    std::snprintf(msg, sizeof msg, "%s: rows [first_row, first_row + num_rows) must lie in [0, total_rows)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if ((double)num_rows * num_chains > (double)kMaxFlat) {
-    std::snprintf(msg, sizeof msg, "%s: num_rows x num_chains must stay below 2^31 per call (accumulate in shorter segments)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (num_rows > 0 && !rows) {
-    std::snprintf(msg, sizeof msg, "%s: null rows", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  int rc = phf_check_positive(who, "num_chains and row_stride_cols", {num_chains, row_stride_cols});
+  if (rc != PHF_OK) return rc;
+  if (row_stride_cols < needed_cols)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: row_stride_cols (%d) is smaller than the columns read (%d)", who, row_stride_cols, needed_cols);
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
+  if ((double)num_rows * num_chains > (double)kMaxFlat)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_rows x num_chains must stay below 2^31 per call (accumulate in shorter segments)", who);
+  if (num_rows > 0 && !rows) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: null rows", who);
   return PHF_OK;
 }
 
@@ -335,11 +304,8 @@ extern "C" int phf_quantiles_init(int num_problems, int num_columns, int curve_p
   static const char* who = "phf_quantiles_init";
   int rc = check_geometry(who, num_problems, num_columns, curve_points, bins);
   if (rc != PHF_OK) return rc;
-  const Layout l = layout_of(num_problems, num_columns, curve_points, bins);
-  if ((rc = check_workspace(who, workspace, workspace_bytes, l)) != PHF_OK) return rc;
-  if ((rc = phf_require_device_memory(workspace, "phf_quantiles_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, l.total(), static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch(who);
-  return PHF_OK;
+  const size_t need = layout_of(num_problems, num_columns, curve_points, bins).total();
+  return phf_init_workspace(who, "quantiles", workspace, workspace_bytes, need, need, stream);
 }
 
 extern "C" int phf_quantiles_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains,
@@ -350,7 +316,7 @@ extern "C" int phf_quantiles_accumulate(const double* rows, int64_t num_rows, in
   if (rc != PHF_OK) return rc;
   if (num_columns < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate: the workspace has no columns");
   if ((rc = check_rows(who, rows, num_rows, row_stride_cols, num_chains, num_columns, first_row, total_rows)) != PHF_OK) return rc;
-  if ((rc = check_workspace(who, workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins))) != PHF_OK) return rc;
+  if ((rc = phf_check_workspace(who, "quantiles", workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins).total())) != PHF_OK) return rc;
   if (num_rows == 0) return PHF_OK;
   QArgs a = args_of(rows, num_rows, num_problems, row_stride_cols, num_chains, num_columns, curve_points, bins, workspace);
   a.first = 0; a.count = num_columns;
@@ -368,7 +334,7 @@ extern "C" int phf_quantiles_accumulate_curves(const double* rows, int64_t num_r
   if (curve_points < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_curves: the workspace has no curve points");
   if (!ln_doses) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_accumulate_curves: null ln_doses");
   if ((rc = check_rows(who, rows, num_rows, row_stride_cols, num_chains, model, first_row, total_rows)) != PHF_OK) return rc;
-  if ((rc = check_workspace(who, workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins))) != PHF_OK) return rc;
+  if ((rc = phf_check_workspace(who, "quantiles", workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins).total())) != PHF_OK) return rc;
   if (num_rows == 0) return PHF_OK;
   QArgs a = args_of(rows, num_rows, num_problems, row_stride_cols, num_chains, num_columns, curve_points, bins, workspace);
   a.ln_dose = ln_doses; a.first = num_columns; a.count = curve_points;
@@ -392,7 +358,7 @@ extern "C" int phf_quantiles_accumulate_hier_curves(const double* rows, int64_t 
   if (total_rows > 4294967296LL)
     return phf_fail(PHF_ERR_INVALID_ARGUMENT,
                     "phf_quantiles_accumulate_hier_curves: total_rows must fit the 32-bit row word of the random stream");
-  if ((rc = check_workspace(who, workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins))) != PHF_OK) return rc;
+  if ((rc = phf_check_workspace(who, "quantiles", workspace, workspace_bytes, layout_of(num_problems, num_columns, curve_points, bins).total())) != PHF_OK) return rc;
   if (num_rows == 0) return PHF_OK;
   QArgs a = args_of(rows, num_rows, num_problems, row_stride_cols, num_chains, num_columns, curve_points, bins, workspace);
   a.ln_dose = ln_doses; a.problem_id = problem_id; a.chain_id_base = chain_id_base;
@@ -422,7 +388,7 @@ extern "C" int phf_quantiles_reduce(int num_problems, int num_columns, int curve
   for (int p = 0; p < num_probs; ++p)
     if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_reduce: probabilities must lie in [0, 1]");
   const Layout l = layout_of(num_problems, num_columns, curve_points, bins);
-  if ((rc = check_workspace(who, workspace, workspace_bytes, l)) != PHF_OK) return rc;
+  if ((rc = phf_check_workspace(who, "quantiles", workspace, workspace_bytes, l.total())) != PHF_OK) return rc;
   if (!out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_quantiles_reduce: null out");
   QReduceArgs a = {};
   a.B = bins; a.S = (int)l.slots; a.P = num_probs;

@@ -157,15 +157,10 @@ __global__ __launch_bounds__(kThreads) void rx_labels_kernel(int P, int R, int C
 }
 
 int check_shape(const char* who, int num_pairs, int rungs, int num_chains) {
-  char msg[kPhfErrorBufferSize];
-  if (num_pairs < 1 || num_chains < 1 || rungs < 2 || rungs > PHF_RX_REPLICA_MASK) {
-    std::snprintf(msg, sizeof msg, "%s: num_pairs and num_chains must be positive and rungs_per_pair at least 2", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if ((double)num_pairs * rungs * num_chains > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: num_pairs * rungs_per_pair * num_chains must fit in an int32", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (num_pairs < 1 || num_chains < 1 || rungs < 2 || rungs > PHF_RX_REPLICA_MASK)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_pairs and num_chains must be positive and rungs_per_pair at least 2", who);
+  if ((double)num_pairs * rungs * num_chains > 2147483647.0)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: num_pairs * rungs_per_pair * num_chains must fit in an int32", who);
   return PHF_OK;
 }
 

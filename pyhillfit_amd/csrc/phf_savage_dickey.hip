@@ -112,34 +112,25 @@ extern "C" int phf_savage_dickey_accumulate(const phf_points* pts, int panels, c
                                             int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int every,
                                             double* accumulators, size_t accumulator_bytes, void* stream) {
   static const char* who = "phf_savage_dickey_accumulate";
-  char msg[kPhfErrorBufferSize];
-  if (!phf_sd_panels_ok(panels)) {
-    std::snprintf(msg, sizeof msg, "%s: panels must be 16, 32 or 64 (got %d)", who, panels);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (!phf_sd_panels_ok(panels))
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: panels must be 16, 32 or 64 (got %d)", who, panels);
   if (!pts || !pts->ln_conc || !pts->response || !pts->weight || !pts->counts)
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_savage_dickey_accumulate: null points");
   if (!nodes || !rows || !accumulators) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_savage_dickey_accumulate: null pointer");
-  if (row_stride_cols != kCols) {
-    std::snprintf(msg, sizeof msg, "%s: row_stride_cols must be %d, the columns of a model-2 row (pIC50, Hill, sigma, log-target), got %d",
-                  who, kCols, row_stride_cols);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (row_stride_cols != kCols)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: row_stride_cols must be %d, the columns of a model-2 row (pIC50, Hill, sigma, log-target), got %d",
+                     who, kCols, row_stride_cols);
   if (every < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_savage_dickey_accumulate: every must be >= 1");
   if (num_chains < 1) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_savage_dickey_accumulate: num_chains must be positive");
   if (num_problems < 1 || pts->num_pairs != num_problems)
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_savage_dickey_accumulate: the points must have one pair per problem");
-  if (pts->stride < 1 || pts->stride > kMaxStride) {
-    std::snprintf(msg, sizeof msg, "%s: 1..%d entries per pair (stride %d)", who, kMaxStride, pts->stride);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (pts->stride < 1 || pts->stride > kMaxStride)
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: 1..%d entries per pair (stride %d)", who, kMaxStride, pts->stride);
   if (num_rows < 0 || first_row < 0) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_savage_dickey_accumulate: num_rows and first_row must be >= 0");
   const int64_t units = (int64_t)num_problems * num_chains;
   if (units > (2147483647ll - kWaves) * kWaves) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_savage_dickey_accumulate: too many (problem, chain) units");
-  if (accumulator_bytes < (size_t)units * PHF_SD_ACC_DOUBLES * sizeof(double)) {
-    std::snprintf(msg, sizeof msg, "%s: the accumulators are smaller than num_problems x num_chains x %d doubles", who, PHF_SD_ACC_DOUBLES);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
+  if (accumulator_bytes < (size_t)units * PHF_SD_ACC_DOUBLES * sizeof(double))
+    return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: the accumulators are smaller than num_problems x num_chains x %d doubles", who, PHF_SD_ACC_DOUBLES);
   const int64_t used = phf_sd_rows_used(first_row, num_rows, every);
   if (used == 0) return PHF_OK;                                          // no row of the call is used: no launch
   SdArgs a = {};

@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_grid.h"
 #include "phf_sensitivity.h"
 
@@ -407,14 +407,11 @@ __global__ __launch_bounds__(kThreads) void sens_reduce_sums_kernel(const RArgs 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
-int fail(const char* who, const char* what) {
-  char msg[kPhfErrorBufferSize];
-  std::snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-}
+int fail(const char* who, const char* what) { return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: %s", who, what); }
 
 int check_geometry(const char* who, int num_problems, int num_columns, int num_chains, int64_t total_rows, int bins) {
-  if (num_problems < 1 || num_columns < 1 || num_chains < 1) return fail(who, "num_problems, num_columns and num_chains must be positive");
+  const int rc = phf_check_positive(who, "num_problems, num_columns and num_chains", {num_problems, num_columns, num_chains});
+  if (rc != PHF_OK) return rc;
   if (total_rows < 1) return fail(who, "total_rows must be positive");
   if (phf_grid_check_bins(who, bins, kMaxBins) != PHF_OK) return PHF_ERR_INVALID_ARGUMENT;
   if ((double)total_rows * num_chains > 4294967296.0) return fail(who, "total_rows x num_chains must not exceed 2^32 draws (the masses' uint64 sums)");
@@ -458,11 +455,7 @@ extern "C" int phf_sensitivity_init(int num_problems, int num_columns, int num_c
   int rc = check_geometry(who, num_problems, num_columns, num_chains, total_rows, bins);
   if (rc != PHF_OK) return rc;
   const Layout l = layout_of(num_problems, num_columns, num_chains, total_rows, bins);
-  if (!workspace) return fail(who, "null workspace");
-  if (workspace_bytes < l.total) return fail(who, "workspace smaller than phf_sensitivity_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_sensitivity_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, l.persistent, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch(who);
-  return PHF_OK;
+  return phf_init_workspace(who, "sensitivity", workspace, workspace_bytes, l.total, l.persistent, stream);
 }
 
 extern "C" int phf_sensitivity_accumulate(int kind, const phf_points* sl_points, const phf_hier_points* hier_points,
@@ -475,7 +468,7 @@ extern "C" int phf_sensitivity_accumulate(int kind, const phf_points* sl_points,
   if (rc != PHF_OK) return rc;
   if (kind < kSingle1 || kind > kGiven) return fail(who, "kind must be 1, 2 (single-level model), 3 (hierarchical) or 4 (given columns)");
   if (!delta_ok(delta)) return fail(who, "delta must satisfy 0 < delta <= 0.25");
-  if (row_stride_cols < 1 || num_columns > row_stride_cols) return fail(who, "row_stride_cols must be at least num_columns");
+  if ((rc = phf_check_row_stride(who, row_stride_cols, num_columns, "must be at least num_columns")) != PHF_OK) return rc;
   int needed = 0;
   if (kind == kSingle1 || kind == kSingle2) {
     if ((rc = check_sl_points(who, sl_points, num_problems)) != PHF_OK) return rc;
@@ -487,13 +480,11 @@ extern "C" int phf_sensitivity_accumulate(int kind, const phf_points* sl_points,
     if (prior_column < 0 || prior_column >= row_stride_cols || likelihood_column < 0 || likelihood_column >= row_stride_cols)
       return fail(who, "the given component columns must lie in [0, row_stride_cols)");
   }
-  if (row_stride_cols < needed) return fail(who, "row_stride_cols is smaller than the columns the model reads");
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return fail(who, "rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
+  if ((rc = phf_check_row_stride(who, row_stride_cols, needed, "is smaller than the columns the model reads")) != PHF_OK) return rc;
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
   if (num_rows > 0 && !rows) return fail(who, "null rows");
-  if (!workspace) return fail(who, "null workspace");
   const Layout l = layout_of(num_problems, num_columns, num_chains, total_rows, bins);
-  if (workspace_bytes < l.total) return fail(who, "workspace smaller than phf_sensitivity_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "sensitivity", workspace, workspace_bytes, l.total)) != PHF_OK) return rc;
   if (num_rows == 0) return PHF_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(workspace);
@@ -550,9 +541,8 @@ extern "C" int phf_sensitivity_reduce(int num_problems, int num_columns, int num
   static const char* who = "phf_sensitivity_reduce";
   int rc = check_geometry(who, num_problems, num_columns, num_chains, total_rows, bins);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return fail(who, "null workspace");
   const Layout l = layout_of(num_problems, num_columns, num_chains, total_rows, bins);
-  if (workspace_bytes < l.total) return fail(who, "workspace smaller than phf_sensitivity_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "sensitivity", workspace, workspace_bytes, l.total)) != PHF_OK) return rc;
   if (!out_slots || !out_weights || !out_columns) return fail(who, "null out");
   const char* base = static_cast<const char*>(workspace);
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pyhillfit_amd.h"
-#include "phf_common.h"
+#include "phf_host_checks.h"
 #include "phf_device_util.h"
 #include "phf_model.h"
 
@@ -211,20 +211,10 @@ __global__ __launch_bounds__(kThreads) void ss_reduce_joint_kernel(const SsArgs 
 }
 
 int check_shape(const char* who, int num_problems, int num_chains, int64_t total_rows) {
-  char msg[kPhfErrorBufferSize];
-  if (num_problems < 1 || num_chains < 1) {
-    std::snprintf(msg, sizeof msg, "%s: num_problems and num_chains must be positive", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if (total_rows < 1) {
-    std::snprintf(msg, sizeof msg, "%s: total_rows must be positive (got %lld)", who, (long long)total_rows);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  if ((double)num_problems * ((num_chains + 63) / 64) > 2147483647.0) {
-    std::snprintf(msg, sizeof msg, "%s: launch grid too large (fewer problems per workspace)", who);
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, msg);
-  }
-  return PHF_OK;
+  const int rc = phf_check_positive(who, "num_problems and num_chains", {num_problems, num_chains});
+  if (rc != PHF_OK) return rc;
+  if (total_rows < 1) return phf_failf(PHF_ERR_INVALID_ARGUMENT, "%s: total_rows must be positive (got %lld)", who, (long long)total_rows);
+  return phf_check_grid(who, {(double)num_problems * ((num_chains + 63) / 64)});
 }
 
 size_t workspace_bytes_of(int num_problems, int num_chains) {
@@ -240,15 +230,11 @@ extern "C" size_t phf_stepping_stone_workspace_bytes(int num_problems, int num_c
 
 extern "C" int phf_stepping_stone_init(int num_problems, int num_chains, int64_t total_rows, double* workspace, size_t workspace_bytes,
                                        void* stream) {
-  int rc = check_shape("phf_stepping_stone_init", num_problems, num_chains, total_rows);
+  static const char* who = "phf_stepping_stone_init";
+  const int rc = check_shape(who, num_problems, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
-  if (!workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_init: null workspace");
   const size_t need = workspace_bytes_of(num_problems, num_chains);
-  if (workspace_bytes < need)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_init: workspace smaller than phf_stepping_stone_workspace_bytes()");
-  if ((rc = phf_require_device_memory(workspace, "phf_stepping_stone_init: workspace")) != PHF_OK) return rc;
-  if (hipMemsetAsync(workspace, 0, need, static_cast<hipStream_t>(stream)) != hipSuccess) return phf_check_launch("phf_stepping_stone_init");
-  return PHF_OK;
+  return phf_init_workspace(who, "stepping_stone", workspace, workspace_bytes, need, need, stream);
 }
 
 extern "C" int phf_stepping_stone_accumulate(const phf_points* pts, int model, const int32_t* pair_index, const double* delta,
@@ -261,14 +247,10 @@ extern "C" int phf_stepping_stone_accumulate(const phf_points* pts, int model, c
       !pts->extra)
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_accumulate: null or empty points");
   if (model != 1 && model != 2) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_accumulate: model must be 1 or 2");
-  if (row_stride_cols < model + 1)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_accumulate: row_stride_cols is smaller than the model's parameters");
-  if (num_rows < 0 || first_row < 0 || first_row + num_rows > total_rows)
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT,
-                    "phf_stepping_stone_accumulate: rows [first_row, first_row + num_rows) must lie in [0, total_rows)");
+  if ((rc = phf_check_row_stride(who, row_stride_cols, model + 1, "is smaller than the model's parameters")) != PHF_OK) return rc;
+  if ((rc = phf_check_row_window(who, num_rows, first_row, total_rows)) != PHF_OK) return rc;
   if (!pair_index || !delta || !rows || !workspace) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_accumulate: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_accumulate: workspace smaller than phf_stepping_stone_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "stepping_stone", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_chains))) != PHF_OK) return rc;
   if (num_rows == 0) return PHF_OK;
   SsArgs a = {};
   a.pts = *pts; a.model = model; a.pair_index = pair_index; a.delta = delta; a.rows = rows; a.nr = num_rows; a.first_row = first_row;
@@ -284,11 +266,11 @@ extern "C" int phf_stepping_stone_accumulate(const phf_points* pts, int model, c
 
 extern "C" int phf_stepping_stone_reduce(int num_problems, int num_chains, int64_t total_rows, const double* workspace,
                                          size_t workspace_bytes, double* out, void* stream) {
-  int rc = check_shape("phf_stepping_stone_reduce", num_problems, num_chains, total_rows);
+  static const char* who = "phf_stepping_stone_reduce";
+  int rc = check_shape(who, num_problems, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
   if (!workspace || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce: null pointer");
-  if (workspace_bytes < workspace_bytes_of(num_problems, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce: workspace smaller than phf_stepping_stone_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "stepping_stone", workspace, workspace_bytes, workspace_bytes_of(num_problems, num_chains))) != PHF_OK) return rc;
   SsArgs a = {};
   a.Q = num_problems; a.C = num_chains; a.total_rows = total_rows; a.ws = const_cast<double*>(workspace); a.out = out;
   hipLaunchKernelGGL(ss_reduce_kernel, dim3(blocks_for(num_problems, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
@@ -300,11 +282,11 @@ extern "C" int phf_stepping_stone_reduce_joint(int num_pairs, int rungs_per_pair
   if (num_pairs < 1 || rungs_per_pair < 1 || (double)num_pairs * rungs_per_pair > 2147483647.0)
     return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce_joint: num_pairs and rungs_per_pair must be positive");
   const int Q = num_pairs * rungs_per_pair;
-  int rc = check_shape("phf_stepping_stone_reduce_joint", Q, num_chains, total_rows);
+  static const char* who = "phf_stepping_stone_reduce_joint";
+  int rc = check_shape(who, Q, num_chains, total_rows);
   if (rc != PHF_OK) return rc;
   if (!workspace || !reduced || !out) return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce_joint: null pointer");
-  if (workspace_bytes < workspace_bytes_of(Q, num_chains))
-    return phf_fail(PHF_ERR_INVALID_ARGUMENT, "phf_stepping_stone_reduce_joint: workspace smaller than phf_stepping_stone_workspace_bytes()");
+  if ((rc = phf_check_workspace(who, "stepping_stone", workspace, workspace_bytes, workspace_bytes_of(Q, num_chains))) != PHF_OK) return rc;
   SsArgs a = {};
   a.Q = Q; a.C = num_chains; a.total_rows = total_rows; a.ws = const_cast<double*>(workspace); a.out = out;
   hipLaunchKernelGGL(ss_reduce_joint_kernel, dim3(blocks_for(num_pairs, kWaves)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a,

@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from .sampler import _ptr, _stream_ptr
 
 BIN_CHOICES = (128, 256, 512, 1024)
@@ -84,21 +84,21 @@ def workspace_bytes(num_problems, num_doses, bins, chains, slots=None):
     return 8 * num_problems * num_doses * (ns * acc_doubles(bins) + 1)
 
 
-class NextDose(object):
+class NextDose(accumulator.RowAccumulator):
     """Streaming EIG sums of num_problems single-level problems (model 1 | 2) over `chains` chains at the candidate doses `doses`
     ([num_problems][G], uM): accumulate() takes the post-burn-in rows in order, a segment at a time, as views of the sampler's row
     buffer [rows][Q][stride][chains] (asynchronous, on the current stream); exactly the global rows r with r mod every == 0 are
     used, however the calls cut them.  result() downloads the sums and finalizes; tested: per problem, the concentrations it has
     data at (for `already_tested`)."""
 
+    tensors = ("acc", "ln_doses")
+
     def __init__(self, model, num_problems, chains, doses, tested=None, bins=DEFAULT_BINS, every=DEFAULT_EVERY, device="cuda", slots=None):
-        self.lib = _lib.load()
         if model not in (1, 2):
             raise ValueError("the next-dose analysis is single-level only (model 1 or 2), got %r" % (model,))
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("NextDose runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         self.model, self.bins, self.every = int(model), check_bins(bins), int(every)
+        self.min_cols = self.model + 1
         if self.every < 1:
             raise ValueError("every must be >= 1, got %r" % (every,))
         self.Q, self.C = int(num_problems), int(chains)
@@ -110,19 +110,11 @@ class NextDose(object):
         self.slots = default_slots(self.Q, self.G, self.C) if slots is None else int(slots)
         self.ln_doses = torch.from_numpy(np.log(d)).to(self.device)
         self.acc = torch.zeros((self.Q, self.G, self.slots, acc_doubles(self.bins)), dtype=torch.float64, device=self.device)
-        self.rows_seen = 0
 
-    def accumulate(self, rows):
-        cols = self.model + 1
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
+    def _accumulate(self, rows, n):
         _lib.check(self.lib.phf_design_accumulate(self.model, self.bins, _ptr(rows), n, self.Q, rows.shape[2], self.C, self.rows_seen,
                                                   self.every, _ptr(self.ln_doses), self.G, self.slots, _ptr(self.acc),
                                                   self.acc.numel() * 8, _stream_ptr(self.device)), "phf_design_accumulate")
-        self.rows_seen += n
 
     def accumulators(self):
         """numpy [Q][G][slots][acc_doubles(bins)]"""
@@ -132,10 +124,6 @@ class NextDose(object):
         """one dict per problem"""
         acc = self.accumulators()
         return [finalize(acc[q], self.doses[q], self.tested[q], self.bins, self.every, self.C) for q in range(self.Q)]
-
-    def free(self):
-        self.acc = None
-        self.ln_doses = None
 
 
 def _entropy(p):

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
@@ -39,11 +39,7 @@ def effective_lags(total_rows, lags=DEFAULT_LAGS):
 
 def workspace_bytes(num_problems, columns, chains, total_rows, lags=DEFAULT_LAGS):
     """device bytes ChainDiagnostics holds: num_problems * columns * chains * (4L + 6) doubles (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_diagnostics_workspace_bytes(int(num_problems), int(columns), int(chains), int(total_rows), int(lags))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_diagnostics_workspace_bytes", num_problems, columns, chains, total_rows, lags)
 
 
 def finalize(mean_acov, xbar_var, h, num_half_chains):
@@ -80,45 +76,28 @@ def finalize(mean_acov, xbar_var, h, num_half_chains):
     return rhat, ess, mcse, limit & moved
 
 
-class ChainDiagnostics(object):
+class ChainDiagnostics(accumulator.RowAccumulator):
     """Streaming diagnostics of num_problems x columns over `chains` chains and total_rows post-burn-in rows.
     accumulate() takes the rows in order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride][chains]
     (asynchronous, on the current stream); result() reduces and finalizes."""
 
     def __init__(self, num_problems, chains, columns, total_rows, lags=DEFAULT_LAGS, device="cuda"):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("ChainDiagnostics runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         self.Q, self.C, self.cols, self.N, self.K = int(num_problems), int(chains), int(columns), int(total_rows), int(lags)
-        self.nbytes = workspace_bytes(self.Q, self.cols, self.C, self.N, self.K)
+        self.min_cols = self.cols
         self.L = effective_lags(self.N, self.K)
         self.h = self.N // 2
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_diagnostics_init(self.Q, self.cols, self.C, self.N, self.K, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                                 _stream_ptr(self.device)), "phf_diagnostics_init")
-        self.rows_seen = 0
+        self._init_workspace(workspace_bytes(self.Q, self.cols, self.C, self.N, self.K), "phf_diagnostics_init", self.Q, self.cols, self.C,
+                             self.N, self.K)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         _lib.check(self.lib.phf_diagnostics_accumulate(_ptr(rows), n, self.Q, rows.shape[2], self.C, self.cols, self.rows_seen, self.N,
                                                        self.K, _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
                    "phf_diagnostics_accumulate")
-        self.rows_seen += n
 
     def reduced(self):
         """[Q][cols][L+3] numpy: mean acov(0..L), mean of the half-chain means, their variance (divisor M-1)"""
-        if self.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.rows_seen, self.N))
+        self._check_complete()
         out = torch.empty((self.Q, self.cols, self.L + 3), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.phf_diagnostics_reduce(self.Q, self.cols, self.C, self.N, self.K, _ptr(self.ws), C.c_size_t(self.nbytes),
                                                    _ptr(out), _stream_ptr(self.device)), "phf_diagnostics_reduce")
@@ -129,9 +108,6 @@ class ChainDiagnostics(object):
         red = self.reduced()
         rhat, ess, mcse, limit = finalize(red[..., :self.L + 1], red[..., self.L + 2], self.h, 2 * self.C)
         return {"rhat": rhat, "ess": ess, "mcse_mean": mcse, "lag_limit_reached": limit}
-
-    def free(self):
-        self.ws = None
 
 
 def diagnose(chains, lags=DEFAULT_LAGS, device="cuda"):

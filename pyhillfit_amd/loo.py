@@ -24,7 +24,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from .sampler import _ptr, _stream_ptr
 from ._lib import _num
 from .waic import GIVEN, DevicePoints, _likelihood, columns_read
@@ -62,11 +62,7 @@ def tail_capacity(num_problems, stride, chains, total_rows, requested=0):
 
 def workspace_bytes(num_problems, stride, chains, total_rows, tail_per_chain=0):
     """device bytes PointwiseLOO holds (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_psis_workspace_bytes(int(num_problems), int(stride), int(chains), int(total_rows), int(tail_per_chain))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_psis_workspace_bytes", num_problems, stride, chains, total_rows, tail_per_chain)
 
 
 def finalize(elpd_loo_i, lppd_i, khat_i, sigma_i, determined_i, S):
@@ -94,45 +90,31 @@ def finalize(elpd_loo_i, lppd_i, khat_i, sigma_i, determined_i, S):
             "n_undetermined": undetermined, "draws": S}
 
 
-class PointwiseLOO(object):
+class PointwiseLOO(accumulator.RowAccumulator):
     """Streaming PSIS-LOO of num_problems problems over `chains` chains and total_rows post-burn-in rows.  accumulate() takes the rows
     in order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride >= columns][chains] (asynchronous, on the
     current stream); result() reduces and finalizes.  kind: 1 | 2 (single-level model), "hierarchical" or "given" (waic.Points.given:
     column p of a row is the log-likelihood of point p); tail_per_chain: the heap
     capacity per (point, chain), 0 for the default rule."""
 
+    tensors = ("ws", "dp")
+
     def __init__(self, points, kind, num_problems, chains, total_rows, device="cuda", tail_per_chain=0):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PointwiseLOO runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         if points.num_problems != int(num_problems):
             raise ValueError("the points have %d problems, not %d" % (points.num_problems, num_problems))
         self.lik, self.ne = _likelihood(kind, points)
-        self.cols = columns_read(kind, points)
+        self.cols = self.min_cols = columns_read(kind, points)
         self.points = points
         self.Q, self.C, self.N = int(num_problems), int(chains), int(total_rows)
         self.requested = int(tail_per_chain)
-        self.nbytes = workspace_bytes(self.Q, points.stride, self.C, self.N, self.requested)
+        nbytes = workspace_bytes(self.Q, points.stride, self.C, self.N, self.requested)
         self.M = tail_length(self.C, self.N)
         self.k = tail_capacity(self.Q, points.stride, self.C, self.N, self.requested)
         self.dp = DevicePoints(points, self.device)
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_psis_init(self.Q, points.stride, self.C, self.N, self.requested, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                          _stream_ptr(self.device)), "phf_psis_init")
-        self.rows_seen = 0
+        self._init_workspace(nbytes, "phf_psis_init", self.Q, points.stride, self.C, self.N, self.requested)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         if self.lik == GIVEN:
             _lib.check(self.lib.phf_psis_accumulate_given(C.byref(self.dp.struct), _ptr(rows), n, self.Q, rows.shape[2], self.C, self.rows_seen,
                                                           self.N, self.requested, _ptr(self.ws), C.c_size_t(self.nbytes),
@@ -141,13 +123,11 @@ class PointwiseLOO(object):
             _lib.check(self.lib.phf_psis_accumulate(C.byref(self.dp.struct), self.lik, self.ne, _ptr(rows), n, self.Q, rows.shape[2], self.C,
                                                     self.rows_seen, self.N, self.requested, _ptr(self.ws), C.c_size_t(self.nbytes),
                                                     _stream_ptr(self.device)), "phf_psis_accumulate")
-        self.rows_seen += n
 
     def reduced(self, tail=False):
         """dict of numpy [Q][stride] arrays elpd_loo, lppd, khat, sigma, determined (NaN / 0 beyond a problem's count); with tail=True
         also "tail": [Q][stride][M + 1], the M + 1 smallest log-likelihoods of every point, ascending"""
-        if self.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.rows_seen, self.N))
+        self._check_complete()
         ps = self.points.stride
         out = torch.empty((5, self.Q, ps), dtype=torch.float64, device=self.device)
         t = torch.empty((self.Q, ps, self.M + 1), dtype=torch.float64, device=self.device) if tail else None
@@ -176,10 +156,6 @@ class PointwiseLOO(object):
             res["insertions_per_draw"] = float(ins[q, :n].sum() / max(1, n * S))
             out.append(res)
         return out
-
-    def free(self):
-        self.ws = None
-        self.dp = None
 
 
 def loo_of_draws(points, kind, draws, device="cuda", tail_per_chain=0):

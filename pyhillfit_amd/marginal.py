@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from . import loo as loo_mod
 from . import waic as waic_mod
 from .sampler import _ptr, _stream_ptr
@@ -147,11 +147,7 @@ class MarginalRows(object):
 
     def __call__(self, rows):
         """the next n post-burn-in rows -> (loglik, gap): device tensors [used][Q][Ne][chains] of the rows used among them"""
-        cols = 5 + 2 * self.ne
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
+        accumulator.check_rows(rows, self.Q, self.C, 5 + 2 * self.ne, self.device)
         n = rows.shape[0]
         used = rows_used(self.rows_seen, n, self.every)
         ll = torch.empty((used, self.Q, self.ne, self.C), dtype=torch.float64, device=self.device)
@@ -190,7 +186,7 @@ def workspace_bytes(num_problems, num_expts, chains, total_rows, every, rows_per
             + 8 * num_problems * num_expts * chains * (1 + 2 * min(call, used)))
 
 
-class ExperimentLOO(object):
+class ExperimentLOO(accumulator.RowAccumulator):
     """Streaming integrated leave-one-experiment-out of num_problems hierarchical problems (all with Ne experiments) over `chains`
     chains and total_rows post-burn-in rows: accumulate() takes the rows in order, a segment at a time, as views of the sampler's row
     buffer; every `every`-th global row goes through the marginal kernel and its [used][Q][Ne][chains] output, the experiments being
@@ -198,7 +194,9 @@ class ExperimentLOO(object):
 
     def __init__(self, points, num_problems, chains, total_rows, nodes=DEFAULT_NODES, every=DEFAULT_EVERY, device="cuda"):
         self.marginal = MarginalRows(points, num_problems, chains, nodes, every, device)
+        accumulator.RowAccumulator.__init__(self, device)
         self.points, self.ne = points, points.num_expts
+        self.min_cols = 5 + 2 * self.ne
         self.nodes, self.every = self.marginal.nodes, self.marginal.every
         self.Q, self.C, self.N = int(num_problems), int(chains), int(total_rows)
         self.used = rows_used(0, self.N, self.every)
@@ -208,9 +206,7 @@ class ExperimentLOO(object):
         self.waic = waic_mod.PointwiseWAIC(self.epoints, "given", self.Q, self.C, self.used, device)
         self.psis = loo_mod.PointwiseLOO(self.epoints, "given", self.Q, self.C, self.used, device)
 
-    def accumulate(self, rows):
-        if self.marginal.rows_seen + rows.shape[0] > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.marginal.rows_seen + rows.shape[0], self.N))
+    def _accumulate(self, rows, n):
         ll, _ = self.marginal(rows)
         if ll.shape[0]:
             self.waic.accumulate(ll)
@@ -219,8 +215,7 @@ class ExperimentLOO(object):
 
     def result(self):
         """one dict per problem"""
-        if self.marginal.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.marginal.rows_seen, self.N))
+        self._check_complete()
         lse, var = self.waic.reduced()
         r = self.psis.reduced()
         gaps = self.marginal.gap_maxima()

@@ -23,7 +23,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from ._lib import _num
 from . import waic as wc
 from .sampler import _ptr, _stream_ptr
@@ -40,11 +40,7 @@ METHOD = ("posterior predictive check (BDA3 ch. 6): per draw one replicate of ev
 
 def workspace_bytes(num_problems, stride, chains, total_rows):
     """device bytes PosteriorPredictiveCheck holds: num_problems * (21 + stride) * chains doubles (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_ppc_workspace_bytes(int(num_problems), int(stride), int(chains), int(total_rows))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_ppc_workspace_bytes", num_problems, stride, chains, total_rows)
 
 
 def finalize(sums, n_points, draws):
@@ -65,22 +61,21 @@ def finalize(sums, n_points, draws):
             "draws": S, "invalid": invalid, "n_points": int(n_points)}
 
 
-class PosteriorPredictiveCheck(object):
+class PosteriorPredictiveCheck(accumulator.RowAccumulator):
     """Streaming posterior predictive check of num_problems problems over `chains` chains and total_rows post-burn-in rows.
     accumulate() takes the rows in order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride >= columns][chains]
     (asynchronous, on the current stream); result() reduces and finalizes.  kind: 1 | 2 (single-level model) or "hierarchical".
     seed, problem_ids (one per problem) and chain_id_base address the random stream: the replicates of a draw depend on them and
     on the draw's (chain, row) alone."""
 
+    tensors = ("ws", "dp")
+
     def __init__(self, points, kind, num_problems, chains, total_rows, seed=25, problem_ids=None, chain_id_base=0, device="cuda"):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PosteriorPredictiveCheck runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         if points.num_problems != int(num_problems):
             raise ValueError("the points have %d problems, not %d" % (points.num_problems, num_problems))
         self.lik, self.ne = wc._likelihood(kind, points)
-        self.cols = wc.columns_read(kind, points)
+        self.cols = self.min_cols = wc.columns_read(kind, points)
         self.points = points
         self.Q, self.C, self.N = int(num_problems), int(chains), int(total_rows)
         self.seed, self.chain_id_base = int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_id_base) & 0xFFFFFFFF
@@ -88,34 +83,19 @@ class PosteriorPredictiveCheck(object):
         if ids.shape != (self.Q,):
             raise ValueError("one problem id per problem: %d expected, got %s" % (self.Q, ids.shape))
         self.problem_ids = ids
-        self.nbytes = workspace_bytes(self.Q, points.stride, self.C, self.N)
+        nbytes = workspace_bytes(self.Q, points.stride, self.C, self.N)
         self.dp = wc.DevicePoints(points, self.device)
         self.pid = torch.from_numpy((ids & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).to(self.device)
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_ppc_init(self.Q, points.stride, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                         _stream_ptr(self.device)), "phf_ppc_init")
-        self.rows_seen = 0
+        self._init_workspace(nbytes, "phf_ppc_init", self.Q, points.stride, self.C, self.N)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         _lib.check(self.lib.phf_ppc_accumulate(C.byref(self.dp.struct), self.lik, self.ne, _ptr(rows), n, self.Q, rows.shape[2], self.C,
                                                self.rows_seen, self.N, _ptr(self.pid), self.chain_id_base, self.seed, _ptr(self.ws),
                                                C.c_size_t(self.nbytes), _stream_ptr(self.device)), "phf_ppc_accumulate")
-        self.rows_seen += n
 
     def reduced(self):
         """numpy [Q][21 + stride]: the sums over all chains (include/pyhillfit_amd.h)"""
-        if self.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.rows_seen, self.N))
+        self._check_complete()
         out = torch.empty((self.Q, HEAD + self.points.stride), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.phf_ppc_reduce(self.Q, self.points.stride, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _ptr(out),
                                            _stream_ptr(self.device)), "phf_ppc_reduce")
@@ -125,10 +105,6 @@ class PosteriorPredictiveCheck(object):
         """one finalize() dict per problem"""
         red = self.reduced()
         return [finalize(red[q], n, self.N * self.C) for q, n in enumerate(self.points.count)]
-
-    def free(self):
-        self.ws = None
-        self.dp = None
 
 
 def replicate(points, kind, problem_index, theta, counters, seed=25, device="cuda"):

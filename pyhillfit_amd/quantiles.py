@@ -23,7 +23,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
@@ -60,11 +60,7 @@ def check_bins(bins):
 
 def workspace_bytes(num_problems, columns, curve_points=0, bins=DEFAULT_BINS):
     """device bytes PosteriorQuantiles holds: num_problems (columns + curve_points) (8 bins + 72) (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_quantiles_workspace_bytes(int(num_problems), int(columns), int(curve_points), int(bins))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_quantiles_workspace_bytes", num_problems, columns, curve_points, bins)
 
 
 def curve_doses(concs, points):
@@ -95,7 +91,7 @@ def hill_curve(model, ln_dose, pic50, hill):
     return 100.0 * (1.0 - 1.0 / (1.0 + np.exp(arg)))
 
 
-class PosteriorQuantiles(object):
+class PosteriorQuantiles(accumulator.RowAccumulator):
     """Streaming quantiles of num_problems x columns over `chains` chains and total_rows post-burn-in rows; with curve_ln_doses
     ([num_problems][G], natural log of the doses) and model 1 | 2 also the Hill curve at G doses per problem.
     accumulate() takes the rows in order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride][chains]
@@ -104,12 +100,11 @@ class PosteriorQuantiles(object):
     underlying effect and D of a future experiment follow the columns; the future experiment's stream is addressed by seed,
     problem_ids ([num_problems], the samplers' global problem ids) and chain_id_base."""
 
+    tensors = ("ws", "ln_doses", "problem_id")
+
     def __init__(self, num_problems, chains, columns, total_rows, probs=DEFAULT_PROBS, bins=DEFAULT_BINS, device="cuda",
                  curve_ln_doses=None, model=None, band_ln_doses=None, seed=0, problem_ids=None, chain_id_base=0):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PosteriorQuantiles runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         self.Q, self.C, self.cols, self.N, self.B = int(num_problems), int(chains), int(columns), int(total_rows), check_bins(bins)
         self.probs = tuple(float(p) for p in probs)
         parse_probs(",".join(repr(p) for p in self.probs))
@@ -136,44 +131,29 @@ class PosteriorQuantiles(object):
             self.seed, self.chain_id_base = int(seed) & 0xFFFFFFFFFFFFFFFF, int(chain_id_base) & 0xFFFFFFFF
             self.ln_doses = torch.from_numpy(ld).to(self.device)
             self.problem_id = torch.from_numpy((ids & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).to(self.device)
-        self.nbytes = workspace_bytes(self.Q, self.cols, self.G, self.B)
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_quantiles_init(self.Q, self.cols, self.G, self.B, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                               _stream_ptr(self.device)), "phf_quantiles_init")
-        self.rows_seen = 0
+        self.min_cols = max(self.cols, 4 if self.D else 0)
+        self._init_workspace(workspace_bytes(self.Q, self.cols, self.G, self.B), "phf_quantiles_init", self.Q, self.cols, self.G, self.B)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        need = max(self.cols, 4 if self.D else 0)
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < need:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, need, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         step = max(1, (2 ** 31 - 1) // self.C)                 # rows x chains < 2^31 per call
         for r0 in range(0, n, step):
             part = rows[r0:r0 + step]
-            m = part.shape[0]
+            m, first = part.shape[0], self.rows_seen + r0
             if self.cols:
                 _lib.check(self.lib.phf_quantiles_accumulate(_ptr(part), m, self.Q, rows.shape[2], self.C, self.cols, self.G, self.B,
-                                                             self.rows_seen, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
+                                                             first, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
                                                              _stream_ptr(self.device)), "phf_quantiles_accumulate")
             if self.D:
                 _lib.check(self.lib.phf_quantiles_accumulate_hier_curves(_ptr(part), m, self.Q, rows.shape[2], self.C, _ptr(self.ln_doses),
-                                                                         self.cols, self.D, self.B, self.rows_seen, self.N,
+                                                                         self.cols, self.D, self.B, first, self.N,
                                                                          _ptr(self.problem_id), self.chain_id_base, self.seed,
                                                                          _ptr(self.ws), C.c_size_t(self.nbytes),
                                                                          _stream_ptr(self.device)), "phf_quantiles_accumulate_hier_curves")
             elif self.G:
                 _lib.check(self.lib.phf_quantiles_accumulate_curves(_ptr(part), m, self.Q, rows.shape[2], self.C, self.model,
-                                                                    _ptr(self.ln_doses), self.cols, self.G, self.B, self.rows_seen,
+                                                                    _ptr(self.ln_doses), self.cols, self.G, self.B, first,
                                                                     self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
                                                                     _stream_ptr(self.device)), "phf_quantiles_accumulate_curves")
-            self.rows_seen += m
 
     def counts(self):
         """the histograms: numpy uint64 [Q][columns + G][B], and the non-finite counts [Q][columns + G]"""
@@ -205,11 +185,6 @@ class PosteriorQuantiles(object):
         if self.D:
             res.update(band_doses=self.D, seed=self.seed)
         return res
-
-    def free(self):
-        self.ws = None
-        self.ln_doses = None
-        self.problem_id = None
 
 
 def quantiles_of_draws(draws, probs=DEFAULT_PROBS, bins=DEFAULT_BINS, device="cuda"):

@@ -20,7 +20,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from . import doseresponse as dr
 from .sampler import DevicePoints, _ptr, _stream_ptr
 
@@ -110,18 +110,17 @@ def workspace_bytes(num_problems, chains, panels=DEFAULT_PANELS):
     return 8 * (num_problems * chains * ACC_DOUBLES + 3 * PANEL_NODES * int(panels))
 
 
-class SavageDickey(object):
+class SavageDickey(accumulator.RowAccumulator):
     """Streaming sums of r for num_problems model-2 problems over `chains` chains: accumulate() takes the post-burn-in rows in order,
     a segment at a time, as views of the sampler's row buffer [rows][Q][4][chains] (asynchronous, on the current stream); exactly
     the global rows r with r mod every == 0 are used, however the calls cut them.  points: the sampler's DevicePoints (or a
     PackedPoints), pair q <-> problem q.  result() downloads the sums and finalizes."""
 
+    tensors = ("acc", "table")
+
     def __init__(self, points, num_problems, chains, panels=DEFAULT_PANELS, every=DEFAULT_EVERY, device="cuda"):
         check_priors()
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("SavageDickey runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         self.panels, self.every = check_panels(panels), int(every)
         if self.every < 1:
             raise ValueError("every must be >= 1, got %r" % (every,))
@@ -133,18 +132,16 @@ class SavageDickey(object):
             raise ValueError("the Savage-Dickey kernel takes at most %d entries per pair, got %d" % (MAX_ENTRIES, self.points.packed.stride))
         self.table = torch.from_numpy(node_table(self.panels)).to(self.device)
         self.acc = torch.zeros((self.Q, self.C, ACC_DOUBLES), dtype=torch.float64, device=self.device)
-        self.rows_seen = 0
 
-    def accumulate(self, rows):
+    def _check_rows(self, rows):
         if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] != 4:
             raise ValueError("rows must be model-2 rows [n][%d][4][%d], got %s" % (self.Q, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
+        accumulator.check_tensor(rows, self.device)
+
+    def _accumulate(self, rows, n):
         _lib.check(self.lib.phf_savage_dickey_accumulate(C.byref(self.points.struct), self.panels, _ptr(self.table), _ptr(rows), n, self.Q,
                                                          rows.shape[2], self.C, self.rows_seen, self.every, _ptr(self.acc),
                                                          self.acc.numel() * 8, _stream_ptr(self.device)), "phf_savage_dickey_accumulate")
-        self.rows_seen += n
 
     def accumulators(self):
         """numpy [Q][C][8]"""
@@ -154,10 +151,6 @@ class SavageDickey(object):
         """one dict per problem"""
         acc = self.accumulators()
         return [finalize(acc[q], self.panels, self.every) for q in range(self.Q)]
-
-    def free(self):
-        self.acc = None
-        self.table = None
 
 
 def _log(v):

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, accumulator
 from ._lib import _num
 
 DEFAULT_DELTA = 0.01
@@ -62,14 +62,10 @@ def check_threshold(t):
 
 def workspace_bytes(num_problems, columns, chains, total_rows, bins=DEFAULT_BINS):
     """device bytes PowerScaling holds (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_sensitivity_workspace_bytes(int(num_problems), int(columns), int(chains), int(total_rows), int(bins))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_sensitivity_workspace_bytes", num_problems, columns, chains, total_rows, bins)
 
 
-class PowerScaling(object):
+class PowerScaling(accumulator.RowAccumulator):
     """Streaming power-scaling sensitivity of num_problems x columns over `chains` chains and total_rows post-burn-in rows.
     points: the sampler's device points (sampler.DevicePoints for kind 1 | 2, hierarchical.DeviceHierPoints — with prior, a
     hierarchical.HierPrior — for kind "hierarchical"), problem q <-> pair q; kind "given": None, and given = (prior column, likelihood
@@ -78,13 +74,9 @@ class PowerScaling(object):
 
     def __init__(self, points, kind, num_problems, chains, columns, total_rows, delta=DEFAULT_DELTA, bins=DEFAULT_BINS, device="cuda",
                  prior=None, given=None, threshold=DEFAULT_THRESHOLD):
-        import torch
         from .sampler import _ptr, _stream_ptr
         self._ptr, self._stream_ptr = _ptr, _stream_ptr
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PowerScaling runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         if kind not in KINDS:
             raise ValueError("kind must be 1, 2, 'hierarchical' or 'given', got %r" % (kind,))
         self.kind, self.code = kind, KINDS[kind]
@@ -98,11 +90,9 @@ class PowerScaling(object):
             self.given = (int(given[0]), int(given[1]))
         elif points is None or (kind == "hierarchical" and prior is None):
             raise ValueError("kind %r needs the model's points%s" % (kind, " and prior" if kind == "hierarchical" else ""))
-        self.nbytes = workspace_bytes(self.Q, self.cols, self.C, self.N, self.B)
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_sensitivity_init(self.Q, self.cols, self.C, self.N, self.B, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                                 _stream_ptr(self.device)), "phf_sensitivity_init")
-        self.rows_seen = 0
+        self.min_cols = self.cols
+        self._init_workspace(workspace_bytes(self.Q, self.cols, self.C, self.N, self.B), "phf_sensitivity_init", self.Q, self.cols, self.C,
+                             self.N, self.B)
 
     def _struct_ptrs(self):
         sl = C.addressof(self.points.struct) if self.code in (1, 2) else None
@@ -110,24 +100,12 @@ class PowerScaling(object):
         pr = C.addressof(self.prior) if self.code == 3 else None
         return sl, hp, pr
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        import torch
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         sl, hp, pr = self._struct_ptrs()
         _lib.check(self.lib.phf_sensitivity_accumulate(self.code, sl, hp, pr, self.given[0], self.given[1], self._ptr(rows), n, self.Q,
                                                        rows.shape[2], self.C, self.cols, self.delta, self.B, self.rows_seen, self.N,
                                                        self._ptr(self.ws), C.c_size_t(self.nbytes), self._stream_ptr(self.device)),
                    "phf_sensitivity_accumulate")
-        self.rows_seen += n
 
     def counts(self):
         """the histograms: numpy uint64 [Q][columns][5][B] (base, prior down, prior up, likelihood down, likelihood up)"""
@@ -158,9 +136,6 @@ class PowerScaling(object):
     def result(self):
         slots, weights, cols = self.reduced()
         return finalize(slots, weights, cols, self.delta, self.threshold, self.rows_seen * self.C, self.B)
-
-    def free(self):
-        self.ws = None
 
 
 def components(points, kind, problem_index, theta, prior=None, device="cuda"):

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from .sampler import DevicePoints, _ptr, _stream_ptr
 
 FIELDS = ("m", "s1", "s2", "sum_ll", "n")
@@ -39,11 +39,7 @@ def deltas(temperatures):
 
 def workspace_bytes(num_problems, chains, total_rows):
     """device bytes SteppingStone holds: num_problems * 5 * chains doubles (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_stepping_stone_workspace_bytes(int(num_problems), int(chains), int(total_rows))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_stepping_stone_workspace_bytes", num_problems, chains, total_rows)
 
 
 def chain_accumulators(ll, delta):
@@ -92,20 +88,20 @@ def finalize(acc):
             "mean_ll": float(np.sum(sl) / (Cn * n[0])), "nan_chains": float(np.sum(np.isnan(lr_c))), "log_r_chains": lr_c}
 
 
-class SteppingStone(object):
+class SteppingStone(accumulator.RowAccumulator):
     """Streaming stepping-stone accumulation of Q rungs (problems) over `chains` chains and total_rows post-burn-in rows.
     packed: the sampler's PackedPoints (or DevicePoints); pair_index[q], delta[q]: problem q's row of the points and its Delta.
     accumulate() takes the rows in order, a segment at a time, as views of the sampler's row buffer [rows][Q][>= d+1][chains]
     (asynchronous, on the current stream); reduced() / result() merge the chains."""
 
+    tensors = ("ws", "points")
+
     def __init__(self, packed, model, pair_index, delta, chains, total_rows, device="cuda"):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("SteppingStone runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         if int(model) not in (1, 2):
             raise ValueError("model must be 1 or 2")
         self.model = int(model)
+        self.min_cols = self.model + 1
         self.points = packed if isinstance(packed, DevicePoints) else DevicePoints(packed, self.device)
         pi = np.asarray(pair_index, dtype=np.int32)
         dl = np.asarray(delta, dtype=np.float64)
@@ -114,32 +110,13 @@ class SteppingStone(object):
         self.Q, self.C, self.N = len(pi), int(chains), int(total_rows)
         self.pair_index = torch.from_numpy(pi).to(self.device)
         self.delta = torch.from_numpy(dl).to(self.device)
-        self.nbytes = workspace_bytes(self.Q, self.C, self.N)
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_stepping_stone_init(self.Q, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                                    _stream_ptr(self.device)), "phf_stepping_stone_init")
-        self.rows_seen = 0
+        self._init_workspace(workspace_bytes(self.Q, self.C, self.N), "phf_stepping_stone_init", self.Q, self.C, self.N)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][Q][>= d + 1][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.model + 1:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.model + 1, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         _lib.check(self.lib.phf_stepping_stone_accumulate(C.byref(self.points.struct), self.model, _ptr(self.pair_index), _ptr(self.delta),
                                                           _ptr(rows), n, self.Q, rows.shape[2], self.C, self.rows_seen, self.N,
                                                           _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
                    "phf_stepping_stone_accumulate")
-        self.rows_seen += n
-
-    def _check_complete(self):
-        if self.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.rows_seen, self.N))
 
     def reduced(self):
         """numpy [Q][7]: the columns of OUT"""
@@ -159,10 +136,6 @@ class SteppingStone(object):
         """one dict per problem (the keys of OUT)"""
         red = self.reduced()
         return [dict(zip(OUT, (float(v) for v in row))) for row in red]
-
-    def free(self):
-        self.ws = None
-        self.points = None
 
 
 def _num(v):

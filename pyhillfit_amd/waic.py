@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, accumulator
 from ._lib import _num
 from .sampler import _ptr, _stream_ptr
 
@@ -140,11 +140,7 @@ def pointwise_loglik(points, kind, problem_index, theta, device="cuda"):
 
 def workspace_bytes(num_problems, stride, chains, total_rows):
     """device bytes PointwiseWAIC holds: num_problems * stride * 5 * chains doubles (raises on an invalid shape)"""
-    lib = _lib.load()
-    n = lib.phf_waic_workspace_bytes(int(num_problems), int(stride), int(chains), int(total_rows))
-    if n == 0:
-        raise ValueError(lib.phf_last_error().decode())
-    return int(n)
+    return accumulator.workspace_bytes("phf_waic_workspace_bytes", num_problems, stride, chains, total_rows)
 
 
 def finalize(lppd_sum_lse, var, S):
@@ -161,41 +157,27 @@ def finalize(lppd_sum_lse, var, S):
             "n_points": int(n), "n_p_waic_above_0.4": int(np.sum(p > P_WARN)), "draws": S}
 
 
-class PointwiseWAIC(object):
+class PointwiseWAIC(accumulator.RowAccumulator):
     """Streaming WAIC of num_problems problems over `chains` chains and total_rows post-burn-in rows.  accumulate() takes the rows in
     order, a segment at a time, as views of the sampler's row buffer [rows][Q][stride >= columns][chains] (asynchronous, on the
     current stream); result() reduces and finalizes.  kind: 1 | 2 (single-level model), "hierarchical", or "given": column p of a
     row IS the log-likelihood of point p (Points.given)."""
 
+    tensors = ("ws", "dp")
+
     def __init__(self, points, kind, num_problems, chains, total_rows, device="cuda"):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("PointwiseWAIC runs on a GPU device, not %s" % self.device)
+        accumulator.RowAccumulator.__init__(self, device)
         if points.num_problems != int(num_problems):
             raise ValueError("the points have %d problems, not %d" % (points.num_problems, num_problems))
         self.lik, self.ne = _likelihood(kind, points)
-        self.cols = columns_read(kind, points)
+        self.cols = self.min_cols = columns_read(kind, points)
         self.points = points
         self.Q, self.C, self.N = int(num_problems), int(chains), int(total_rows)
-        self.nbytes = workspace_bytes(self.Q, points.stride, self.C, self.N)
+        nbytes = workspace_bytes(self.Q, points.stride, self.C, self.N)
         self.dp = DevicePoints(points, self.device)
-        self.ws = torch.empty((self.nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.phf_waic_init(self.Q, points.stride, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes),
-                                          _stream_ptr(self.device)), "phf_waic_init")
-        self.rows_seen = 0
+        self._init_workspace(nbytes, "phf_waic_init", self.Q, points.stride, self.C, self.N)
 
-    def accumulate(self, rows):
-        """rows: contiguous float64 device tensor [n][num_problems][stride >= columns][chains], the next n post-burn-in rows"""
-        if rows.dim() != 4 or rows.shape[1] != self.Q or rows.shape[3] != self.C or rows.shape[2] < self.cols:
-            raise ValueError("rows must be [n][%d][>= %d][%d], got %s" % (self.Q, self.cols, self.C, tuple(rows.shape)))
-        if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != self.device:
-            raise ValueError("rows must be a contiguous float64 tensor on %s" % self.device)
-        n = rows.shape[0]
-        if self.rows_seen + n > self.N:
-            raise ValueError("%d rows would exceed total_rows = %d" % (self.rows_seen + n, self.N))
-        if n == 0:
-            return
+    def _accumulate(self, rows, n):
         if self.lik == GIVEN:
             _lib.check(self.lib.phf_waic_accumulate_given(C.byref(self.dp.struct), _ptr(rows), n, self.Q, rows.shape[2], self.C, self.rows_seen,
                                                           self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
@@ -204,12 +186,10 @@ class PointwiseWAIC(object):
             _lib.check(self.lib.phf_waic_accumulate(C.byref(self.dp.struct), self.lik, self.ne, _ptr(rows), n, self.Q, rows.shape[2], self.C,
                                                     self.rows_seen, self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _stream_ptr(self.device)),
                        "phf_waic_accumulate")
-        self.rows_seen += n
 
     def reduced(self):
         """(LSE, var): numpy [Q][stride] each (meaningless beyond a problem's count)"""
-        if self.rows_seen != self.N:
-            raise ValueError("only %d of %d rows accumulated" % (self.rows_seen, self.N))
+        self._check_complete()
         out = torch.empty((2, self.Q, self.points.stride), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.phf_waic_reduce(self.Q, self.points.stride, self.C, self.N, _ptr(self.ws), C.c_size_t(self.nbytes), _ptr(out),
                                             _stream_ptr(self.device)), "phf_waic_reduce")
@@ -221,10 +201,6 @@ class PointwiseWAIC(object):
         lse, var = self.reduced()
         S = self.N * self.C
         return [finalize(lse[q, :n], var[q, :n], S) for q, n in enumerate(self.points.count)]
-
-    def free(self):
-        self.ws = None
-        self.dp = None
 
 
 def waic_of_draws(points, kind, draws, device="cuda"):

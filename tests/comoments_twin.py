@@ -21,7 +21,7 @@ void v_reduce(const double* ws, int Q, int C, int d, int64_t total_rows, double*
 int v_fields(int d) { return PHF_CM_FIELDS(d); }
 int v_out_doubles(int d) { return PHF_CM_OUT_DOUBLES(d); }
 int v_pair(int d, int i, int j) { return phf_cm_pair(d, i, j); }
-int v_half_of(int64_t total_rows, int64_t n) { int64_t m; return phf_cm_half_of(total_rows, n, &m); }
+int v_half_of(int64_t total_rows, int64_t n) { int64_t m; return phf_half_of(total_rows, n, &m); }
 """
 
 

@@ -23,17 +23,13 @@ int v_x0(int half) { return phf_bm_x0(half); }
 /* one accumulate call as the device entry cuts it: rows [num_rows][stride][C] = rows first_row.. of total_rows, columns 0..cols-1,
  * st [cols][fields][C] */
 void v_accumulate(const double* rows, int64_t num_rows, int64_t first_row, int64_t total_rows, int stride, int cols, int C, double* st) {
-  const int64_t h = total_rows / 2;
-  const int nl = phf_bm_levels(h);
-  const int64_t half_begin[2] = {0, total_rows - h};
+  const int nl = phf_bm_levels(total_rows / 2);
   for (int half = 0; half < 2; ++half) {
-    const int64_t lo = first_row > half_begin[half] ? first_row : half_begin[half];
-    const int64_t end = first_row + num_rows, hend = half_begin[half] + h;
-    const int64_t hi = end < hend ? end : hend;
-    if (lo >= hi) continue;
+    phf_half_segment seg;
+    if (!phf_half_cut(total_rows, first_row, num_rows, half, &seg)) continue;
     for (int j = 0; j < cols; ++j)
       for (int c = 0; c < C; ++c)
-        phf_bm_rows(rows + ((size_t)(lo - first_row) * stride + j) * C + c, (size_t)stride * C, hi - lo, lo - half_begin[half], half,
+        phf_bm_rows(rows + ((size_t)seg.offset * stride + j) * C + c, (size_t)stride * C, seg.nr, seg.m0, half,
                     st + (size_t)j * PHF_BM_FIELDS(nl) * C + c, (size_t)C, nl);
   }
 }
@@ -42,7 +38,7 @@ void v_push_all(const double* x, int64_t total_rows, int C, double* st) {
   const int nl = phf_bm_levels(total_rows / 2);
   for (int64_t n = 0; n < total_rows; ++n) {
     int64_t m;
-    const int half = phf_bm_half_of(total_rows, n, &m);
+    const int half = phf_half_of(total_rows, n, &m);
     if (half < 0) continue;
     for (int c = 0; c < C; ++c) {
       double* s = st + c;
