@@ -852,6 +852,40 @@ int phf_savage_dickey_accumulate(const phf_points* pts, int panels, const double
                                  int num_problems, int row_stride_cols, int num_chains, int64_t first_row, int every,
                                  double* accumulators, size_t accumulator_bytes, void* stream);
 
+/* ---- Drug profile: the joint multi-channel block of a drug at given concentrations ------------------------------------------------
+ * (pyhillfit_amd/csrc/phf_drug_profile.hip, phf_drug_profile.h; DESIGN.md §3, "Drug profile").  A drug has num_channels channel
+ * places; channel_problem[drug][k] names the problem whose single-level rows hold the fit of channel k, -1 (or anything outside
+ * [0, num_problems)) when it was not loaded.  Row r, chain c of every loaded channel side by side is one draw of the drug's joint
+ * posterior.  Per draw and dose j: block_k = 100 (1 - 1/(1 + exp(Hill_k (ln c_j - ln IC50_k)))) as phf_quantiles_accumulate_curves
+ * computes it, net = SUM_k weights[k] block_k over the loaded channels in order (plain multiplies and adds), dominant = the least k
+ * with the largest block_k.  A draw in which a loaded channel's pIC50 or Hill is not finite is counted as non-finite in that
+ * channel's slots and the net slot, and as skipped in the tallies.
+ *   workspace   device, phf_drug_profile_workspace_bytes(...): first a quantiles workspace (above) of num_drugs problems, no columns
+ *               and num_doses (num_channels + 1) curve points — slot (drug, j, k) is curve point j (num_channels + 1) + k, k =
+ *               num_channels the net block; the slots of a channel that was not loaded stay empty — then, at
+ *               phf_drug_profile_tally_offset(...) bytes, uint64 [num_drugs][num_doses][2][num_channels + 3]: per chain parity (chain
+ *               index & 1) the draws whose dominant channel is k, the draws with net > 0, the draws used, the draws skipped
+ *   rows        device [num_rows][num_problems][row_stride_cols][num_chains], column 0 pIC50 and, model 2, column 1 Hill
+ *   channel_problem, weights, ln_doses   device int32 [num_drugs][num_channels], double [num_channels], double [num_drugs][num_doses]
+ *               (natural log of the dose in uM; a drug with fewer doses than num_doses has NaN in the places it does not use: their
+ *               slots and tallies stay empty)
+ *   num_channels <= 16, num_doses <= 16, bins a power of two in [64, 32768], num_rows x num_chains < 2^31 per call
+ * phf_drug_profile_reduce writes what phf_quantiles_reduce writes for those curve points, [slots][8 + 4 num_probs], by calling it.
+ * Everything kept is an integer count: the workspace is bit-identical however the rows are cut into calls.  Every argument is checked
+ * before any launch: PHF_ERR_INVALID_ARGUMENT without touching a GPU (phf_last_error() says why). */
+size_t phf_drug_profile_workspace_bytes(int num_drugs, int num_channels, int num_doses, int bins);   /* 0 for an invalid shape */
+size_t phf_drug_profile_tally_offset(int num_drugs, int num_channels, int num_doses, int bins);      /* 0 for an invalid shape */
+/* the default weight of a channel by its name: +1 hERG, KvLQT1_mink, Kv4.3, Kir2.1; -1 Nav1.5-peak, Nav1.5-late, Cav1.2; else 0 */
+double phf_drug_profile_default_weight(const char* channel);
+int phf_drug_profile_init(int num_drugs, int num_channels, int num_doses, int bins, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int phf_drug_profile_accumulate(const double* rows, int64_t num_rows, int num_problems, int row_stride_cols, int num_chains, int model,
+                                int num_drugs, int num_channels, int num_doses, const int32_t* channel_problem, const double* weights,
+                                const double* ln_doses, int bins, int64_t first_row, int64_t total_rows, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int phf_drug_profile_reduce(int num_drugs, int num_channels, int num_doses, int bins, const double* probs, int num_probs,
+                            const void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@
            [--hierarchical --de-every K [--de-population 64] [--de-gamma GAMMA] [--de-jump-every 10]]
            [--next-dose G [--next-dose-concs c1,c2,...] [--next-dose-bins 256] [--next-dose-every 17]] [--correlations]
            [-m 2 --savage-dickey [--savage-dickey-panels 32] [--savage-dickey-every 11]]
+           [--drug-profile-concs c1,c2,... | --drug-profile-cmax FILE [--drug-profile-multiples 1,3,10]] [--drug-profile-weights name=w,...]
+           [--drug-profile-bins 4096]
 
 Same command-line flags, same output files in the same places (python/PyHillFit.py:33-65,645-971; chain-file
 contract: doseresponse.py:70-82,115-128), but every selected (drug, channel) pair is sampled AT ONCE by the HIP
@@ -34,7 +36,10 @@ gain of one further measurement at G candidate doses (pyhillfit_amd/design.py), 
 parameter columns and the multivariate R-hat with the direction along which the chains sit apart (pyhillfit_amd/correlations.py),
 accumulated the same way and written as "correlations"; with -m 2 --savage-dickey, the Bayes factor B12 of Hill = 1 against Hill free by
 the Savage-Dickey density ratio from this run's draws alone (pyhillfit_amd/savage_dickey.py), accumulated the same way and written as
-"bayes_factor".  The CMA-ES start point is replaced by a deterministic least-squares fit
+"bayes_factor"; with --drug-profile-concs or --drug-profile-cmax (single-level), the joint multi-channel block of every drug at the given
+concentrations — per channel and as a weighted net block, with the probability that the net block is positive and of each channel being
+the most blocked one (pyhillfit_amd/drug_profile.py) — accumulated the same way and written to one
+`<drug>/drug_profiles/<drug>_drug_profile.json` per drug.  The CMA-ES start point is replaced by a deterministic least-squares fit
 (bestfit.py); figures are not produced (plotting is outside the sampling step).
 
 Multi-GPU: `-c/--num-cores N` — the reference's pool size (python/PyHillFit.py:40,997-1003) — starts min(N, visible GPUs) ranks,
@@ -158,6 +163,7 @@ def check_args(parser, args):
         args.savage_dickey_every = sd.DEFAULT_EVERY if args.savage_dickey_every is None else args.savage_dickey_every
         if args.savage_dickey_every < 1:
             parser.error("--savage-dickey-every must be >= 1")
+    check_drug_profile_args(parser, args)
     de_given = [n for n in ("de_population", "de_gamma", "de_jump_every") if getattr(args, n, None) is not None]
     if args.de_every < 0:
         parser.error("--de-every must be >= 0 (0 = no differential-evolution moves)")
@@ -174,6 +180,38 @@ def check_args(parser, args):
             de.check_settings(args.de_every, args.thinning, args.de_population, chains, args.de_gamma, args.de_jump_every)
         except ValueError as e:
             parser.error("--de-every / --de-population / --de-gamma / --de-jump-every: " + str(e))
+
+
+def check_drug_profile_args(parser, args):
+    """the --drug-profile-* flags: args.drug_profile says whether the analysis is on; the values are parsed in place"""
+    from . import drug_profile as dp
+    args.drug_profile = args.drug_profile_concs is not None or args.drug_profile_cmax is not None
+    given = [n for n in ("drug_profile_multiples", "drug_profile_weights", "drug_profile_bins") if getattr(args, n) is not None]
+    if given and not args.drug_profile:
+        parser.error("--%s needs --drug-profile-concs or --drug-profile-cmax" % given[0].replace("_", "-"))
+    if not args.drug_profile:
+        return
+    if args.hierarchical:
+        parser.error("--drug-profile-concs / --drug-profile-cmax are single-level only: a drug's pairs fall into different launch groups of "
+                     "the hierarchical sampler; profile hierarchical chain files with `python -m pyhillfit_amd.drug_profile --hierarchical`")
+    if args.drug_profile_multiples is not None and args.drug_profile_cmax is None:
+        parser.error("--drug-profile-multiples needs --drug-profile-cmax (the multiples are of Cmax)")
+    try:
+        if isinstance(args.drug_profile_concs, str):
+            args.drug_profile_concs = dp.parse_concs(args.drug_profile_concs)
+        args.drug_profile_multiples = (dp.DEFAULT_MULTIPLES if args.drug_profile_multiples is None else
+                                       dp.parse_multiples(args.drug_profile_multiples))
+        if isinstance(args.drug_profile_cmax, str):
+            args.drug_profile_cmax = dp.read_cmax(args.drug_profile_cmax)
+        if isinstance(args.drug_profile_weights, str):
+            args.drug_profile_weights = dp.parse_weights(args.drug_profile_weights)
+        args.drug_profile_bins = dp.check_bins(dp.DEFAULT_BINS if args.drug_profile_bins is None else args.drug_profile_bins)
+        doses = len(args.drug_profile_concs or ()) + (len(args.drug_profile_multiples) if args.drug_profile_cmax is not None else 0)
+        if doses > dp.MAX_DOSES:
+            raise ValueError("at most %d doses per drug (--drug-profile-concs and --drug-profile-multiples together), got %d"
+                             % (dp.MAX_DOSES, doses))
+    except (ValueError, OSError) as e:
+        parser.error(str(e))
 
 
 def build_parser():
@@ -279,6 +317,22 @@ def build_parser():
     new.add_argument("--savage-dickey-every", type=int, default=None, metavar="T", help="--savage-dickey: every T-th post-burn-in row of every "
                      "chain is used (default 11: on the whole Crumb set at the default chains and P = 32 the flag then adds no more than the "
                      "sampling time; the cost grows with P / T)")
+    new.add_argument("--drug-profile-concs", type=str, default=None, metavar="c1,c2,...", help="single-level: the drug profile at these "
+                     "concentrations (uM, the same for every drug): per post-burn-in draw of all the channels of a drug side by side, the "
+                     "percent block of every channel, their weighted net block and the most blocked channel; quantiles at the "
+                     "--quantile-probs, the probability of a positive net block and of each channel being the most blocked, from "
+                     "histograms and integer counts accumulated on the GPU while the rows stream past; written to one "
+                     "<drug>/drug_profiles/<drug>_drug_profile.json per drug.  Not an action-potential prediction, not a risk category")
+    new.add_argument("--drug-profile-cmax", type=str, default=None, metavar="FILE", help="single-level: the drug profile at multiples of "
+                     "each drug's clinical concentration; FILE as the reference's chaste/drug_list.txt: a header line, then `Drug "
+                     "EFTPCmax(nM) [anything]`; a drug the file does not name is skipped unless --drug-profile-concs is given too")
+    new.add_argument("--drug-profile-multiples", type=str, default=None, metavar="m1,...", help="--drug-profile-cmax: the multiples of "
+                     "Cmax (default 1,3,10: a convention)")
+    new.add_argument("--drug-profile-weights", type=str, default=None, metavar="name=w,...", help="the drug profile's weights of the net "
+                     "block by channel name, overriding the defaults: +1 hERG, KvLQT1_mink, Kv4.3, Kir2.1, -1 Nav1.5-peak, Nav1.5-late, "
+                     "Cav1.2, 0 any other name — a convention (repolarising minus depolarising block), not a measurement")
+    new.add_argument("--drug-profile-bins", type=int, default=None, metavar="B", help="the drug profile's histogram bins per channel and "
+                     "dose, a power of two in [64, 32768] (default 4096)")
     new.add_argument("--de-every", type=int, default=0, metavar="K", help="--hierarchical: differential-evolution moves between the chains of "
                      "each pair (ter Braak 2006) after every K iterations, K a multiple of the thinning (default 0 = off: every output as "
                      "without the flag); the chains of one population are then coupled; written to the summary JSON as \"de_moves\"")
@@ -373,6 +427,7 @@ def run_single_level(pairs, args, device, rank=0, world=1):
     aset = an.AnalysisSet(kinds, an.Run(
         args=args, kind=model, Q=Q, C=C, cols=d + 1, columns=columns, saved=saved_iterations, burn=burn, device=device,
         sampler_points=s.points, concs=[concs for _, _, concs, _ in loaded], seed=args.seed, problem_ids=problem_ids, prior=None, de=None,
+        pairs=[(drug, channel) for drug, channel, _, _ in loaded],
         make_points=lambda: Points.single_level(*zip(*[experiments_and_labels(drug, channel) for drug, channel, _, _ in loaded]))))
     aset.feed_start(s.row0)
     kept = (torch.empty((saved_iterations, Q, d + 1, C), dtype=torch.float64, device=device) if keep_all else
@@ -477,7 +532,10 @@ def _run(args, rank, local_rank, world):
                 costs.append(sum(len(e) for e in dr.load_crumb_data(d, c)[2]))
             except Exception:
                 costs.append(0)
-        mine = phfdist.shard_problems(costs, world)[rank]
+        if getattr(args, "drug_profile", False):                       # a drug's channels are paired row by row: whole drugs to a rank
+            mine = phfdist.shard_drugs(costs, [d for d, _ in pairs], world)[rank]
+        else:
+            mine = phfdist.shard_problems(costs, world)[rank]
         pairs = [pairs[i] for i in mine]
     if args.hierarchical:
         from .hierarchical import run_hierarchical

@@ -31,7 +31,9 @@ EXPORTS = ["phf_version", "phf_last_error", "phf_simd_count", "phf_single_level_
            "phf_batch_means_levels", "phf_batch_means_init", "phf_batch_means_accumulate", "phf_batch_means_reduce",
            "phf_design_accumulator_doubles", "phf_design_rows_used", "phf_design_accumulate", "phf_comoments_workspace_bytes",
            "phf_comoments_init", "phf_comoments_accumulate", "phf_comoments_reduce", "phf_savage_dickey_accumulator_doubles",
-           "phf_savage_dickey_nodes", "phf_savage_dickey_rows_used", "phf_savage_dickey_accumulate"]
+           "phf_savage_dickey_nodes", "phf_savage_dickey_rows_used", "phf_savage_dickey_accumulate", "phf_drug_profile_workspace_bytes",
+           "phf_drug_profile_tally_offset", "phf_drug_profile_default_weight", "phf_drug_profile_init", "phf_drug_profile_accumulate",
+           "phf_drug_profile_reduce"]
 
 
 class PhfError(RuntimeError):
@@ -188,6 +190,15 @@ def load():
     lib.phf_savage_dickey_rows_used.argtypes = [i64, i64, i32]
     lib.phf_savage_dickey_rows_used.restype = i64
     lib.phf_savage_dickey_accumulate.argtypes = [C.POINTER(Points), i32, vp, vp, i64, i32, i32, i32, i64, i32, vp, C.c_size_t, vp]
+    lib.phf_drug_profile_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.phf_drug_profile_workspace_bytes.restype = C.c_size_t
+    lib.phf_drug_profile_tally_offset.argtypes = [i32, i32, i32, i32]
+    lib.phf_drug_profile_tally_offset.restype = C.c_size_t
+    lib.phf_drug_profile_default_weight.argtypes = [C.c_char_p]
+    lib.phf_drug_profile_default_weight.restype = f64
+    lib.phf_drug_profile_init.argtypes = [i32, i32, i32, i32, vp, C.c_size_t, vp]
+    lib.phf_drug_profile_accumulate.argtypes = [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i64, i64, vp, C.c_size_t, vp]
+    lib.phf_drug_profile_reduce.argtypes = [i32, i32, i32, i32, vp, i32, vp, C.c_size_t, vp, vp]
     _lib = lib
     return lib
 

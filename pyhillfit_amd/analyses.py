@@ -15,6 +15,7 @@ reports; `AnalysisSet` holds the analyses of one sampler in a fixed order and is
 
 A new row analysis is one adapter and one entry in fit_analyses() or tempered_analyses()."""
 import functools
+import json
 
 import numpy as np
 import torch
@@ -24,6 +25,8 @@ from . import correlations as cr
 from . import de_moves as de
 from . import design as ds
 from . import diagnostics as dg
+from . import doseresponse as dr
+from . import drug_profile as dp
 from . import loo as lo
 from . import marginal as mg
 from . import ppc as pp
@@ -52,7 +55,8 @@ class Run(object):
     how many of them are burn-in), device, sampler_points.  The fits also: make_points (-> waic.Points of the problems, built once,
     when an analysis first asks for `points`), concs (per problem, its concentrations), seed, problem_ids, prior, de (the sampler's
     DEMoves or None).  Hierarchical also: seg_rows, cdf_chains, writers, rng_pred, fitted_all (per problem).  Tempered also:
-    pair_index, rung_index (per problem), temperatures, num_pairs, swap."""
+    pair_index, rung_index (per problem), temperatures, num_pairs, swap.  Single-level fits also: pairs (per problem, its (drug,
+    channel))."""
 
     def __init__(self, **facts):
         self.__dict__.update(facts)
@@ -359,13 +363,58 @@ class SavageDickeyBF(Analysis):
         summ["bayes_factor"] = sd.json_record(self.res[q])
 
 
+class DrugProfile(Analysis):
+    """--drug-profile-concs / --drug-profile-cmax: the joint multi-channel block of every drug at its doses (single-level only); a
+    file of its own per drug instead of summary keys, written when the drug's first pair is recorded.  `records`: per profiled drug"""
+    what = "--drug-profile-concs / --drug-profile-cmax"
+    hint = "histograms, {:.1f} GB are free: select fewer drugs, fewer doses or a smaller --drug-profile-bins"
+
+    def make(self, run):
+        a = run.args
+        clean = dr._clean                                                 # the names the files carry: KvLQT1/mink -> KvLQT1_mink
+        try:
+            self.plan = p = dp.Plan([(clean(d), clean(c)) for d, c in run.pairs], [clean(c) for c in dr.channels],
+                                    a.drug_profile_concs, a.drug_profile_cmax, a.drug_profile_multiples, a.drug_profile_weights)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        self.records = []
+        if not p.drugs:
+            return None
+        shape = (len(p.drugs), len(p.channels), p.doses.shape[1], a.drug_profile_bins)
+        self.check(dp.workspace_bytes(*shape))
+        return dp.DrugProfile(run.kind, run.Q, run.C, p.map, p.weights, p.doses, run.rows, a.quantile_probs, a.drug_profile_bins, run.device)
+
+    def accumulate(self, rows):
+        if self.acc is not None:
+            self.acc.accumulate(rows)
+
+    def finish(self):
+        if self.acc is None:
+            return
+        res, p = self.acc.result(), self.plan
+        self.acc.free()
+        self.records = [dp.json_record(res, d, drug, p.channels, p.cmax[d], p.multiples) for d, drug in enumerate(p.drugs)]
+        self.writes_at = {p.first_problem(d): d for d in range(len(p.drugs))}
+
+    def record(self, summ, q):
+        d = self.writes_at.get(q) if self.records else None
+        if d is not None:
+            with open(dr.drug_profile_file(self.plan.drugs[d]), "w") as f:
+                json.dump(self.records[d], f, indent=1)
+
+    @classmethod
+    def report(cls, rank, names, group, args):
+        return [dp.report_line(rank, [r for a in group for r in a.records], [d for a in group for d in a.plan.skipped])]
+
+
 def fit_analyses(args):
     """the analyses of a PyHillFit run, single-level or hierarchical, in the order they are built, fed, recorded and reported"""
     table = [(args.hierarchical and args.predictive_cdfs, PredictiveCdfs), (args.diagnostics, Diagnostics),
              (args.diagnostic_batch_means, BatchMeans), (args.de_every, DeMoves), (args.waic, Waic), (args.loo, Loo),
              (args.leave_experiment_out, ExperimentLoo), (args.quantiles, Quantiles), (args.ppc, Ppc), (args.sensitivity, Sensitivity),
              (args.next_dose and not args.hierarchical, Design), (args.correlations, Correlations),
-             (args.savage_dickey and not args.hierarchical, SavageDickeyBF)]
+             (args.savage_dickey and not args.hierarchical, SavageDickeyBF),
+             (getattr(args, "drug_profile", False) and not args.hierarchical, DrugProfile)]   # (set by check_args)
     return [kind for on, kind in table if on]
 
 

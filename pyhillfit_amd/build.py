@@ -18,7 +18,7 @@ TEXTIO_LIB = os.path.join(LIB_DIR, "libphf_textio.so")
 SOURCES = ["phf_capi.hip", "phf_single_level.hip", "phf_hierarchical.hip", "phf_predictive.hip", "phf_hier3_isa.hip",
            "phf_diagnostics.hip", "phf_pointwise.hip", "phf_psis.hip", "phf_quantiles.hip", "phf_ppc.hip",
            "phf_stepping_stone.hip", "phf_replica_exchange.hip", "phf_hier_marginal.hip", "phf_sensitivity.hip", "phf_hier_de.hip",
-           "phf_batch_means.hip", "phf_design.hip", "phf_comoments.hip", "phf_savage_dickey.hip"]
+           "phf_batch_means.hip", "phf_design.hip", "phf_comoments.hip", "phf_savage_dickey.hip", "phf_drug_profile.hip"]
 # the hand-allocated gfx950 code object: generated assembly (tools/gen_hier_isa.py; committed) -> .o -> .co, embedded by phf_hier3_isa.hip
 ISA_SRC = os.path.join(CSRC, "generated", "phf_hier3_gfx950.s")
 ISA_CO = os.path.join(LIB_DIR, "obj", "phf_hier3_gfx950.co")

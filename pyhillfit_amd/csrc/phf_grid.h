@@ -9,7 +9,7 @@
  * unit is compiled with -ffp-contract=off and nothing here is an fma, so every build gives the same bins.
  *
  * Part A, the scalar rule, compiles as C11 with gcc (the tests' ground truth) and into the kernels.  Parts B (the device code: the
- * prepare pass, the bin index of a value, the output head) and C (the host's sizing and refusal) are for hipcc only. */
+ * prepare pass, the bin index of a value, the bin pass, the output head) and C (the host's sizing and refusal) are for hipcc only. */
 #ifndef PHF_GRID_H
 #define PHF_GRID_H
 
@@ -151,6 +151,44 @@ __device__ inline int phf_grid_index(const phf_grid_view& g, double x, int B) {
     if (__builtin_isfinite(t)) j = phf_grid_bin(t, g.level, B);
   }
   return j;
+}
+
+// the bin pass of one workgroup of THREADS threads over the call's values [i0, i1) of a slot: a workgroup-private uint32 histogram in
+// LDS (s_hist, the workgroup's dynamic LDS, [B]; a wavefront whose lanes all fall in one bin adds once), flushed to the slot's uint64
+// counts with integer atomics for its non-zero bins only; the values counted apart go to *nonfinite.  value(i) as in phf_grid_prepare.
+template <int THREADS, typename Value>
+__device__ __forceinline__ void phf_grid_bin_values(const double* h, unsigned long long* cnt, unsigned long long* nonfinite, int B,
+                                                    unsigned i0, unsigned i1, unsigned* s_hist, Value value) {
+  const phf_grid_view grid = phf_grid_load(h);
+  const int tid = threadIdx.x;
+  for (int j = tid; j < B; j += THREADS) s_hist[j] = 0u;
+  __syncthreads();
+  unsigned nf = 0;
+  const int lane = __lane_id();
+  for (unsigned i = i0 + tid; i < i1; i += THREADS) {
+    const double x = value(i);
+    const int j = phf_grid_index(grid, x, B);
+    nf += j < 0;
+    const unsigned long long active = __ballot(1);
+    const int j0 = __builtin_amdgcn_readfirstlane(j);
+    if (__ballot(j != j0) == 0) {                                // the whole wavefront in one bin (a stuck or constant column)
+      if (j0 >= 0 && lane == __ffsll((long long)active) - 1) atomicAdd(&s_hist[j0], (unsigned)__popcll(active));
+    } else if (j >= 0) {
+      atomicAdd(&s_hist[j], 1u);
+    }
+  }
+  __syncthreads();
+  for (int j = tid; j < B; j += THREADS) {
+    const unsigned c = s_hist[j];
+    if (c) atomicAdd(&cnt[j], (unsigned long long)c);
+  }
+  if (nf) atomicAdd(nonfinite, (unsigned long long)nf);
+}
+
+// the values [i0, i1) of split `split` of a bin launch (phf_grid_split_of, below) over n values
+__device__ inline void phf_grid_split_range(unsigned n, int split, unsigned per_split, unsigned* i0, unsigned* i1) {
+  *i0 = (unsigned)split * per_split;
+  *i1 = *i0 >= n ? *i0 : (n - *i0 < per_split ? n : *i0 + per_split);   // [i0, i1) within [0, n)
 }
 
 // the kGridOutHead doubles a reduce writes per slot

@@ -128,33 +128,10 @@ __global__ __launch_bounds__(kBinThreads) void q_bin_kernel(const QArgs a) {
   const int slot = blockIdx.x / a.splits;
   const int q = slot / a.count, k = slot % a.count;
   const size_t s = (size_t)q * a.spp + a.first + k;
-  const phf_grid_view grid = phf_grid_load(a.hdr + s * kHdr);
-  const int tid = threadIdx.x;
-  for (int j = tid; j < a.B; j += kBinThreads) s_hist[j] = 0u;
-  __syncthreads();
-  const unsigned i0 = (unsigned)split * a.per_split;
-  const unsigned i1 = i0 >= a.n ? i0 : (a.n - i0 < a.per_split ? a.n : i0 + a.per_split);   // [i0, i1) within [0, n)
-  unsigned nf = 0;
-  const int lane = __lane_id();
-  for (unsigned i = i0 + tid; i < i1; i += kBinThreads) {
-    const double x = q_value<MODEL>(a, q, k, i, k_exp, k_log);
-    const int j = phf_grid_index(grid, x, a.B);
-    nf += j < 0;
-    const unsigned long long active = __ballot(1);
-    const int j0 = __builtin_amdgcn_readfirstlane(j);
-    if (__ballot(j != j0) == 0) {                                // the whole wavefront in one bin (a stuck or constant column)
-      if (j0 >= 0 && lane == __ffsll((long long)active) - 1) atomicAdd(&s_hist[j0], (unsigned)__popcll(active));
-    } else if (j >= 0) {
-      atomicAdd(&s_hist[j], 1u);
-    }
-  }
-  __syncthreads();
-  unsigned long long* cnt = a.counts + s * a.B;
-  for (int j = tid; j < a.B; j += kBinThreads) {
-    const unsigned c = s_hist[j];
-    if (c) atomicAdd(&cnt[j], (unsigned long long)c);
-  }
-  if (nf) atomicAdd(&a.nonfinite[s], (unsigned long long)nf);
+  unsigned i0, i1;
+  phf_grid_split_range(a.n, split, a.per_split, &i0, &i1);
+  phf_grid_bin_values<kBinThreads>(a.hdr + s * kHdr, a.counts + s * a.B, a.nonfinite + s, a.B, i0, i1, s_hist,
+                                   [&](unsigned i) { return q_value<MODEL>(a, q, k, i, k_exp, k_log); });
 }
 
 // ---- reduce ------------------------------------------------------------------------------------------------------------------------

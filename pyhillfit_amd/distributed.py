@@ -145,6 +145,22 @@ def shard_problems(costs, world):
     return [np.array(sorted(p), dtype=np.int64) for p in parts]
 
 
+def shard_drugs(costs, drug_of_problem, world):
+    """Partition problems over ranks with every drug whole on one rank (the drug profile pairs the rows of a drug's channels):
+    longest-processing-time greedy over the drugs, a drug costing the sum of its problems, deterministic (ties: the drug that appears
+    first, the lowest rank).  Returns a list of index arrays, one per rank."""
+    costs = np.asarray(costs, dtype=np.float64)
+    names = list(dict.fromkeys(drug_of_problem))
+    members = {d: [q for q, dq in enumerate(drug_of_problem) if dq == d] for d in names}
+    per_drug = np.array([costs[members[d]].sum() for d in names])
+    load = np.zeros(world)
+    parts = [[] for _ in range(world)]
+    for i in np.argsort(-per_drug, kind="stable"):
+        r = int(np.argmin(load))
+        parts[r] += members[names[int(i)]]; load[r] += per_drug[i]
+    return [np.array(sorted(p), dtype=np.int64) for p in parts]
+
+
 def shard_blocks(costs, blocks_per_problem, world):
     """Partition the (problem, 64-chain block) UNITS of a batch over ranks, balancing cost: longest-processing-time greedy over
     the units (every block of a problem costs what the problem costs per chain), deterministic.  The reference's unit of

@@ -343,6 +343,15 @@ def nonhierarchical_chain_file_and_figs_dir(model, drug, channel, temperature, m
     return drug, channel, chain_file, images_dir
 
 
+def drug_profile_file(drug, make_dirs=True):
+    """the profile of one drug over its channels (pyhillfit_amd/drug_profile.py): next to the drug's chain directories"""
+    drug = _clean(drug)
+    output_dir = '{}/{}/single-level/{}/drug_profiles/'.format(output_root, dir_name, drug)
+    if make_dirs:
+        _mk(output_dir)
+    return output_dir + '{}_drug_profile.json'.format(drug)
+
+
 def hierarchical_posterior_predictive_cdf_files(drug, channel, Ne):
     """doseresponse.py:93-99 (names as cleaned by hierarchical_output_dirs_and_chain_file)."""
     cdf_dir = '{}/{}/hierarchical/{}/{}/{}_expts/cdfs/'.format(output_root, dir_name, drug, channel, Ne)
